@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: image-pairs/s of PWC-Net inference at 1024x448 fp32 on N MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR]
 
 With --gpus N > 1 and no WORLD_SIZE in the environment the script starts its own ranks
 (`python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py <same arguments>` as a
@@ -128,6 +128,39 @@ def event_time_ms(fns, reps, stream):
 def last_conv_kernel():
     from opticalflow_amd import _lib
     return _lib.load().pwc_last_conv_kernel().decode()
+
+
+DUMP_CAP_BYTES = 64 << 20     # --dump-outputs: at most this many bytes of .npy files in all
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES, seed=DUMP_SEED):
+    """--dump-outputs: write each tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy in float32 (float64 stays float64),
+    so that two builds can be compared output for output.  Smallest first, an array is written whole while it fits its share of
+    what is left of `cap`; a larger one becomes a fixed sample of that many elements (flat indices drawn with `seed`, ascending).
+    Returns {name: (shape, elements written)}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    items = []
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        items.append((name, np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)))
+    items.sort(key=lambda it: it[1].nbytes)
+    header = 128                                     # bytes of an .npy header (format 1.0, short shape)
+    left, written = cap, {}
+    for i, (name, a) in enumerate(items):
+        share = left // (len(items) - i) - header
+        out = a
+        if a.nbytes > share:
+            k = max(0, share // a.itemsize)
+            out = a.reshape(-1)[np.sort(np.random.default_rng(seed).choice(a.size, size=k, replace=False))]
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, out)
+        left -= os.path.getsize(path)
+        written[name] = (a.shape, out.size)
+        log("dump: %s %s -> %s (%s)" % (name, list(a.shape), path,
+                                         "whole" if out is a else "sample of %d elements, seed %d" % (out.size, seed)))
+    return written
 
 
 PROBE_REPS = 30
@@ -305,10 +338,13 @@ def bench_kitti(args, rank, world, dev, rehearse):
         def __getitem__(self, i):
             return pool[(i // world) % len(pool)]
 
+    last_full = [None]
+
     def run(steps):
         last = None
         for _, full, gathered in stream.run(Repeat(steps * B * world)):
             last = gathered if rank == 0 else full
+            last_full[0] = full
         torch.cuda.synchronize()
         return last
 
@@ -327,6 +363,9 @@ def bench_kitti(args, rank, world, dev, rehearse):
         tmax = torch.tensor([elapsed], device="cpu" if rehearse else dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step: rank 0's own full-resolution flows [B, 2, 375, 1242] and the quarter-resolution flows of all ranks
+        dump_outputs(args.dump_outputs, {"flow_full": last_full[0], "flow_quarter": last[1]})
     if rank == 0:
         pairs = world * B * args.steps
         ok = last is not None and bool(torch.isfinite(last[1]).all())
@@ -398,7 +437,12 @@ def main():
     ap.add_argument("--sync-gather", action="store_true", help="N > 1: wait for each step's flow gather before the next forward (round-3 behaviour, for A/B)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (the flows a caller receives) as DIR/<name>.npy, "
+                         "float32, at most 64 MB in all (a fixed seeded sample of a larger output); rank 0 only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.precision is None:
         # configs[4] names fp16; the half-precision mode that meets north_star's tolerance is the strict one (the fast mode: --precision fp16)
         args.precision = "fp16-strict" if args.workload == "kitti" else "fp32"
@@ -489,6 +533,9 @@ def main():
         tmax = torch.tensor([elapsed], device="cpu" if rehearse else dev, dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         elapsed = float(tmax.item())
+    if args.dump_outputs and rank == 0:
+        # the last timed step's flows [B * world, 2, H/4, W/4] (N > 1: as gathered on rank 0), before anything else runs the net again
+        dump_outputs(args.dump_outputs, {"flow": out if torch.is_tensor(out) else gather.result(out)})
 
     result = None
     fp32 = args.precision == "fp32"

@@ -381,6 +381,28 @@ def test_bench_self_launches_its_ranks(monkeypatch):
     assert not seen and "WORLD_SIZE=2" in str(ei.value.code)
 
 
+def test_bench_dump_outputs_cap_and_sample(tmp_path):
+    """bench.py --dump-outputs: small outputs are written whole as float32 .npy; when the total exceeds the cap the largest array
+    becomes a fixed seeded sample (same elements on every run) and the files stay within the cap."""
+    import bench
+    g = torch.Generator().manual_seed(5)
+    small = torch.rand(2, 2, 3, 4, generator=g, dtype=torch.float32)
+    big = torch.rand(4, 2, 50, 60, generator=g, dtype=torch.float32)
+    wrote = bench.dump_outputs(str(tmp_path / "a"), {"flow": small, "big": big.double()})
+    assert np.array_equal(np.load(tmp_path / "a" / "flow.npy"), small.numpy())
+    assert np.load(tmp_path / "a" / "big.npy").dtype == np.float64
+    assert wrote == {"flow": ((2, 2, 3, 4), small.numel()), "big": ((4, 2, 50, 60), big.numel())}
+
+    cap = 4096 + 2 * 128
+    for d in ("b", "c"):
+        wrote = bench.dump_outputs(str(tmp_path / d), {"flow": small, "big": big}, cap=cap)
+        assert sum(f.stat().st_size for f in (tmp_path / d).iterdir()) <= cap
+    assert wrote["flow"] == ((2, 2, 3, 4), small.numel()) and 0 < wrote["big"][1] < big.numel()
+    sb, sc = np.load(tmp_path / "b" / "big.npy"), np.load(tmp_path / "c" / "big.npy")
+    assert sb.dtype == np.float32 and sb.ndim == 1 and np.array_equal(sb, sc)
+    assert np.isin(sb, big.numpy().reshape(-1)).all()
+
+
 def test_strict_mode_default_filter_policy(monkeypatch):
     """The strict half mode's default since round 4: split (hi + lo) filters on EVERY level-2 / context layer (the error of the mode is
     relative to the flow magnitude, so the faster ladder step's 13 % margin was a property of the test inputs); PWC_STRICT_PLAIN=fast
