@@ -18,6 +18,7 @@
  *   pwc_corr_bwd        correlation_cuda.backward correlation_cuda.cc:89-167, kernels .cu:150-334
  *   pwc_warp_fwd        PWCDCNet.warp             models/PWCNet.py:141-177
  *   pwc_warp_bwd        autograd of the same (grid_sample backward as used by the training scripts)
+ *   pwc_warp_corr81_bwd autograd of corr(c1, warp(c2, s*flo)) + LeakyReLU, PWCNet.py:212-214 etc. (train.py's loss.backward())
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -35,7 +36,7 @@
 extern "C" {
 #endif
 
-#define PWC_ABI_VERSION 12
+#define PWC_ABI_VERSION 13
 
 /* element types */
 #define PWC_F32 0
@@ -135,6 +136,29 @@ int pwc_corr_bwd(const void *in1, const void *in2, const void *grad_out, void *g
                  int pad_size, int kernel_size, int max_disp, int stride1, int stride2,
                  float corr_multiply, int dtype, unsigned flags,
                  void *stream);
+
+/* Gradients of pwc_warp_corr81_fwd (flo != NULL) or of pwc_corr_fwd in PWC-Net's configuration (flo == NULL: level 6, no warp),
+ * the fused LeakyReLU included, in one pass (csrc/pwc_warp_corr_bwd.hip):
+ *   y = act(scale * sum_c c1[p,c] * warp(c2, flow_scale * flo)[p+d,c])    (pad 4, max displacement 4, strides 1, 81 displacements)
+ * c1, c2: [B,C,H,W]; flo: [B,2,H,W] or NULL; y, gy: [B,81,H,W] (y = the forward's ACTIVATED output, read for the LeakyReLU mask
+ * y > 0; only with PWC_ACT_LEAKY, may be NULL otherwise); flags, corr_multiply, leaky_slope, flow_scale, align_corners and
+ * mask_threshold as in the forward.  Outputs dense (contiguous): grad_c1, grad_c2 [B,C,H,W], grad_flo [B,2,H,W] (unused with
+ * flo == NULL).  Input batch strides in elements, C/H/W planes dense.  Semantics of autograd on the reference's expression: the
+ * warp's validity mask is a constant (PWCNet.py:174-175 thresholds it in place), d/dflo goes through the sample coordinates.
+ * Bit-reproducible: grad_c1 and the warped tensor's gradient are gathers with a fixed order; the scatter into grad_c2 (warp form)
+ * accumulates 64-bit fixed-point integers in `workspace` (>= pwc_warp_corr81_bwd_workspace_bytes, 8-byte aligned; required with
+ * flo, unused without), scale 2^(39 - floor(log2 M)) with M = 81 * max|gy| * |scale| * max(1,|slope|) * max|c1|, a bound on every
+ * contribution (resolution 2^-39 of M; 2^23 contributions of the bound per element before an int64 could wrap).  Non-finite gy or
+ * c1: float atomics for that call's grad_c2 (no synchronisation; last bits then order-dependent), as pwc_warp_bwd.
+ * The workspace also holds the per-16-channel-chunk partial sums of grad_flo, added in chunk order by a final pass.
+ * f32 only.  PWC_EUNSUPPORTED (nothing launched) unless every operand is 4-byte aligned, max(C,81)*H*W < 2^31 and the grid fits. */
+int64_t pwc_warp_corr81_bwd_workspace_bytes(int B, int C, int H, int W);
+int pwc_warp_corr81_bwd(const void *c1, const void *c2, const void *flo, const void *y, const void *gy,
+                        void *grad_c1, void *grad_c2, void *grad_flo, int B, int C, int H, int W,
+                        float flow_scale, int align_corners, float mask_threshold, float corr_multiply,
+                        unsigned flags, float leaky_slope,
+                        int64_t c1_bstride, int64_t c2_bstride, int64_t flo_bstride, int64_t y_bstride, int64_t gy_bstride,
+                        void *workspace, int64_t workspace_bytes, void *stream);
 
 /* Backward warp of x by (flow_scale * flo): bilinear, zero padding, times the validity mask
  * [sum of in-bounds bilinear weights >= mask_threshold]  (PWCNet.py:141-177).

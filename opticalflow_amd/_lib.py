@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # PWC_HIP_LIB: alternative build of the same C ABI (kernel experiments); default = the in-tree library
 LIB_PATH = os.environ.get("PWC_HIP_LIB") or os.path.join(_HERE, "libpwc_hip.so")
 
-ABI_VERSION = 12
+ABI_VERSION = 13
 PWC_F32, PWC_F16 = 0, 1
 FLAG_CORR_NORMALIZE = 1
 FLAG_ACT_LEAKY = 2
@@ -43,6 +43,9 @@ SIGNATURES = {
     "pwc_warp_bwd_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "pwc_warp_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                              c_float, c_int, c_float, c_int, c_void_p, c_int64, c_void_p]),
+    "pwc_warp_corr81_bwd_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "pwc_warp_corr81_bwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_float, c_uint, c_float]
+                            + [c_int64] * 5 + [c_void_p, c_int64, c_void_p]),
     "pwc_conv3x3_packed_bytes": (c_int64, [c_int, c_int, c_int]),
     "pwc_conv3x3_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "pwc_conv2d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

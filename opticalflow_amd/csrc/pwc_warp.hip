@@ -18,6 +18,7 @@
 // (2*C + 2)*H*W*sizeof(T) per image.
 #include "pwc_common.h"
 #include "pwc_warp_taps.h"
+#include "pwc_absmax.h"
 
 namespace {
 
@@ -117,20 +118,10 @@ int launch_warp(const void *x, const void *flo, void *out, int B, int C, int H, 
 //                d ix / d u = flow_scale * W / max(W-1,1)        (align_corners = 0)
 //                           = flow_scale * (W-1) / max(W-1,1)    (align_corners = 1).
 // The mask is a constant: the reference thresholds it in place (PWCNet.py:174-175), which cuts its graph.
-// largest |grad_out| as float bits (order-independent: max), into *out (zeroed before).  The bit pattern of |v| orders like the
-// value for finite numbers and puts +inf (0x7f800000) and every NaN (> 0x7f800000) above them, so a non-finite gradient leaves
-// *out >= 0x7f800000: the fixed-point path cannot represent it and the kernels below switch to float atomics for that call
+// largest |grad_out| as float bits (pwc_absmax.h), into the workspace's tail (zeroed before).  A non-finite gradient leaves it
+// >= kNonFiniteBits: the fixed-point path cannot represent it and the kernels below switch to float atomics for that call
 // (Inf / NaN then propagate into grad_x exactly as in the float path and in torch's grid_sample backward).
-constexpr unsigned kNonFiniteBits = 0x7f800000u;
-__global__ void __launch_bounds__(256)
-absmax_kernel(const float *__restrict__ v, int64_t n, unsigned *out) {
-    unsigned m = 0;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256)
-        m = max(m, __float_as_uint(fabsf(v[i])));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) m = max(m, (unsigned)__shfl_xor((int)m, o));
-    if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
-}
+constexpr unsigned kNonFiniteBits = pwc::kAbsmaxNonFinite;
 
 // fixed-point scale for a tensor whose largest magnitude has float bits `mbits`: 2^(40 - exponent)
 __device__ __forceinline__ float fixed_scale(unsigned mbits) {
@@ -260,8 +251,7 @@ extern "C" int pwc_warp_bwd(const void *x, const void *flo, const void *grad_out
         hipError_t e = hipMemsetAsync(workspace, 0, (size_t)nel * 8 + 16, st);
         if (e == hipSuccess) e = hipMemsetAsync(grad_x, 0, (size_t)nel * sizeof(float), st);     // target of the non-finite fallback
         if (e != hipSuccess) { pwc::set_error("pwc_warp_bwd: hipMemsetAsync: %s", hipGetErrorString(e)); return (int)e; }
-        const int mblk = (int)((nel + 255) / 256 < 2048 ? (nel + 255) / 256 : 2048);
-        hipLaunchKernelGGL(absmax_kernel, dim3((unsigned)mblk), dim3(256), 0, st, gf, nel, mbits);
+        pwc::launch_absmax_bits(gf, nel, nel, 1, mbits, st);
         hipLaunchKernelGGL(warp_bwd_kernel<true>, dim3((unsigned)nblk), dim3(kWarpThreads), 0, st, xf, ff, gf,
                            static_cast<float *>(grad_x), acc, mbits, static_cast<float *>(grad_flo), C, H, W, npix,
                            flow_scale, align_corners, mask_threshold);

@@ -219,6 +219,89 @@ class WarpFunction(torch.autograd.Function):
         return gx, gf, None, None, None
 
 
+def warp_correlation_backward(c1: torch.Tensor, c2: torch.Tensor, flo: Optional[torch.Tensor], y: torch.Tensor,
+                              grad_y: torch.Tensor, flow_scale: float = 1.0, align_corners: bool = False,
+                              mask_threshold: float = 0.9999, corr_multiply: float = 1.0, normalize: bool = False,
+                              leaky_slope: Optional[float] = 0.1, fused: bool = True):
+    """(grad_c1, grad_c2, grad_flo) of y = act(correlation(c1, warp(c2, flow_scale * flo))) in PWC-Net's configuration (pad 4, k 1,
+    d 4, strides 1; act = LeakyReLU(leaky_slope), None = no activation); flo None = no warp (level 6), grad_flo is then None.
+    y is the forward's activated output (its sign is the LeakyReLU mask).  fused (default): one pass of pwc_warp_corr81_bwd,
+    bit-reproducible.  Where that entry declines the geometry (PWC_EUNSUPPORTED), or with fused=False, the same gradients come
+    from warp_fwd -> mask in torch -> corr_bwd -> warp_bwd (also deterministic; summation order differs)."""
+    lib = _lib.load()
+    c1, c2, y, grad_y = densify(c1), densify(c2), densify(y), densify(grad_y)
+    B, C, H, W = c1.shape
+    for name, t, shp in (("c1", c1, (B, C, H, W)), ("c2", c2, (B, C, H, W)), ("y", y, (B, 81, H, W)), ("grad_y", grad_y, (B, 81, H, W))) \
+            + ((("flo", flo, (B, 2, H, W)),) if flo is not None else ()):
+        if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != c1.device:
+            raise ValueError("%s must be float32 %s on %s, got %s %s" % (name, shp, c1.device, t.dtype, tuple(t.shape)))
+    if flo is not None:
+        flo = densify(flo)
+    if fused:
+        bs = [_plane_dense(t, n) for t, n in ((c1, "c1"), (c2, "c2"), (y, "y"), (grad_y, "grad_y"))]
+        bsf = _plane_dense(flo, "flo") if flo is not None else 0
+        g1 = torch.empty((B, C, H, W), dtype=torch.float32, device=c1.device)
+        g2 = torch.empty_like(g1)
+        gf = torch.empty((B, 2, H, W), dtype=torch.float32, device=c1.device) if flo is not None else None
+        ws, ws_bytes = None, 0
+        if flo is not None:
+            ws_bytes = lib.pwc_warp_corr81_bwd_workspace_bytes(B, C, H, W)
+            ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=c1.device)
+        flags = (FLAG_CORR_NORMALIZE if normalize else 0) | (FLAG_ACT_LEAKY if leaky_slope is not None else 0)
+        with torch.cuda.device(c1.device):
+            rc = lib.pwc_warp_corr81_bwd(c1.data_ptr(), c2.data_ptr(), flo.data_ptr() if flo is not None else None, y.data_ptr(),
+                                         grad_y.data_ptr(), g1.data_ptr(), g2.data_ptr(), gf.data_ptr() if gf is not None else None,
+                                         B, C, H, W, float(flow_scale), 1 if align_corners else 0, float(mask_threshold),
+                                         float(corr_multiply), flags, float(leaky_slope or 0.0), bs[0], bs[1], bsf, bs[2], bs[3],
+                                         ws.data_ptr() if ws is not None else None, ws_bytes, _stream(c1))
+        if rc != -2:                               # PWC_EUNSUPPORTED: take the composition below
+            check(rc, "pwc_warp_corr81_bwd")
+            return g1, g2, gf
+    g = grad_y if leaky_slope is None else torch.where(y > 0, grad_y, grad_y * leaky_slope)
+    if flo is None:
+        g1, g2 = correlation_backward(c1.contiguous(), c2.contiguous(), g.contiguous(), 4, 1, 4, 1, 1, corr_multiply, normalize)
+        return g1, g2, None
+    c2, flo = c2.contiguous(), flo.contiguous()
+    w2 = warp(c2, flo, flow_scale, align_corners, mask_threshold)
+    g1, gw2 = correlation_backward(c1.contiguous(), w2, g.contiguous(), 4, 1, 4, 1, 1, corr_multiply, normalize)
+    g2, gf = warp_backward(c2, flo, gw2, flow_scale, align_corners, mask_threshold)
+    return g1, g2, gf
+
+
+class WarpCorrelationFunction(torch.autograd.Function):
+    """autograd of one PWC-Net cost volume, act(corr(c1, warp(c2, flow_scale * flo))) (PWCNet.py:212-214, 226-228, 240-242,
+    256-258; flo None: corr(c1, c2) of level 6, :197-198): forward = the fused forward kernel where the library prefers it (else
+    warp + correlation), backward = pwc_warp_corr81_bwd.  Under torch.autocast the inputs are cast to float32 (the kernels are
+    f32 only).  apply(c1, c2, flo, flow_scale, align_corners, mask_threshold, corr_multiply, normalize, leaky_slope)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, c1, c2, flo, flow_scale=1.0, align_corners=False, mask_threshold=0.9999, corr_multiply=1.0,
+                normalize=False, leaky_slope=0.1):
+        c1, c2 = c1.contiguous(), c2.contiguous()
+        flo = flo.contiguous() if flo is not None else None
+        B, C, H, W = c1.shape
+        y = None
+        if flo is not None:
+            if warp_correlation_preferred(B, C, H, W):
+                y = warp_correlation(c1, c2, flo, flow_scale, align_corners, mask_threshold, corr_multiply, normalize, leaky_slope)
+            if y is None:
+                y = correlation(c1, warp(c2, flo, flow_scale, align_corners, mask_threshold), 4, 1, 4, 1, 1, corr_multiply,
+                                normalize, leaky_slope)
+        else:
+            y = correlation(c1, c2, 4, 1, 4, 1, 1, corr_multiply, normalize, leaky_slope)
+        ctx.save_for_backward(c1, c2, flo, y)
+        ctx.cfg = (flow_scale, align_corners, mask_threshold, corr_multiply, normalize, leaky_slope)
+        return y
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_y):
+        c1, c2, flo, y = ctx.saved_tensors
+        g1, g2, gf = warp_correlation_backward(c1, c2, flo, y, grad_y.to(torch.float32).contiguous(), *ctx.cfg)
+        return g1, g2, gf, None, None, None, None, None, None
+
+
 def pack_conv3x3(weight: torch.Tensor) -> torch.Tensor:
     """[Cout,Cin,3,3] nn.Conv2d filter bank -> kernel-native packed buffer (device, float32)."""
     lib = _lib.load()

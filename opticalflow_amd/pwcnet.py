@@ -20,8 +20,14 @@ the checkpoint-loading factories ``pwc_dc_net(path)`` / ``pwc_dc_net_old(path)``
 semantics a checkpoint was trained with (``normalize_corr=True``, see ``_checkpoint_kwargs``), ``conv_backend`` ('hip' = MFMA implicit-GEMM
 kernels, 'torch' = BASELINE config[1], convolutions left to PyTorch-ROCm), ``use_graph``.
 
-Inference only: the HIP path does not build an autograd graph (returned flows have
-``requires_grad=False``).  Tensors must live on a ROCm device; there is no CPU execution path.
+Training: with ``trainable=True`` (constructor / factories), a forward in training mode with grad enabled runs an eager
+autograd path in the reference's order (PWCNet.py:180-273; the old variant's from :407): the convolutions are the module's
+own ``nn.Conv2d`` / ``nn.ConvTranspose2d`` children (PyTorch-ROCm supplies their backward), every cost volume is
+``ops.WarpCorrelationFunction`` (fused warp + correlation + LeakyReLU, forward and backward on HIP kernels), and the
+graph-connected 5-tuple ``(flow2, flow3, flow4, flow5, flow6)`` is returned (fp32 only).  Everything else -- eval mode,
+``torch.no_grad()``, ``trainable=False`` -- runs the HIP inference plans, which build no autograd graph (returned flows
+have ``requires_grad=False``; ``trainable=False`` in training mode warns about it).  Tensors must live on a ROCm device;
+there is no CPU execution path.
 """
 from __future__ import annotations
 
@@ -35,7 +41,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import PwcHipError
 from .correlation import Correlation, onnx_correlation_enabled
-from .engine import (CONTEXT, DENSE_OUT, PYRAMID_CH, PYRAMID_NAMES, PYRAMID_NAMES_OLD, PwcPlan,
+from .engine import (CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PYRAMID_NAMES, PYRAMID_NAMES_OLD, WARP_SCALE, PwcPlan,
                      level_in_channels)
 from .weights import load_checkpoint, synthetic_state_dict
 
@@ -52,7 +58,8 @@ class PWCDCNet(nn.Module):
     _pyramid_names = PYRAMID_NAMES
 
     def __init__(self, md: int = 4, normalize_corr: bool = False, align_corners: bool = False,
-                 conv_backend: str = "hip", use_graph: bool = False, precision: str = "fp32", borrow_output: bool = False):
+                 conv_backend: str = "hip", use_graph: bool = False, precision: str = "fp32", borrow_output: bool = False,
+                 trainable: bool = False):
         super().__init__()
         if precision not in ("fp32", "fp16", "fp16-strict"):
             raise ValueError("precision must be 'fp32', 'fp16' or 'fp16-strict'")
@@ -71,6 +78,8 @@ class PWCDCNet(nn.Module):
         # of the same geometry overwrites it (one 5 us copy less per forward; for callers that consume the flow at once, like the
         # sharded benchmark loop, whose gather copies it into its own staging buffer)
         self.borrow_output = bool(borrow_output)
+        # trainable: training-mode forwards with grad enabled take the eager autograd path (_forward_trainable)
+        self.trainable = bool(trainable)
 
         # registration order == reference order (PWCNet.py:52-132)
         for lvl, (na, naa, nb) in enumerate(self._pyramid_names, start=1):
@@ -125,6 +134,8 @@ class PWCDCNet(nn.Module):
         return ops.warp(ops.densify(x), ops.densify(flo), 1.0, self.align_corners, thr)
 
     def forward(self, x: torch.Tensor):
+        if self.trainable and self.training and torch.is_grad_enabled():
+            return self._forward_trainable(x)
         if self.training and torch.is_grad_enabled() and not self._warned_detached:
             # the convolutions have no backward kernels (Correlation and warp do): say so instead of silently handing a
             # training loop flows that do not require grad
@@ -150,6 +161,60 @@ class PWCDCNet(nn.Module):
         if self.training:
             return tuple(t.clone() for t in plan.flows())
         return out if self.borrow_output else out.clone()
+
+    def _forward_trainable(self, x: torch.Tensor):
+        """The reference's forward (PWCNet.py:180-273; PWCDCNet_old: :407-491) as an autograd graph: the module's own
+        convolution children, cost volumes through ops.WarpCorrelationFunction.  Returns (flow2, flow3, flow4, flow5, flow6)."""
+        if self.precision != "fp32":
+            raise NotImplementedError("trainable=True runs in fp32 only (precision=%r): build the net with precision='fp32' "
+                                      "to train it" % self.precision)
+        if x.dim() != 4 or x.shape[1] != 6:
+            raise ValueError("expected [B,6,H,W] (two stacked 3-channel images), got %s" % (tuple(x.shape),))
+        if not x.is_cuda:
+            raise PwcHipError("PWCDCNet.forward needs a tensor on the ROCm device (got %s): the HIP path has no "
+                              "CPU fallback" % x.device)
+        normalize = self._normalize_now()
+        thr = 0.9999 if self.variant == "dc" else 0.999                      # PWCNet.py:174 / :400
+
+        def cost_volume(c1, c2, flo, scale):
+            return ops.WarpCorrelationFunction.apply(c1, c2, flo, scale, self.align_corners, thr, 1.0, normalize, LEAKY)
+
+        feats = []
+        for im in (x[:, :3], x[:, 3:]):
+            pyr, t = [], im
+            for na, naa, nb in self._pyramid_names:
+                t = getattr(self, na)(t)
+                if naa is not None:
+                    t = getattr(self, naa)(t)
+                t = getattr(self, nb)(t)
+                pyr.append(t)
+            feats.append(pyr)                                                # index 0 -> level 1 ... 5 -> level 6
+        flows = {}
+        up_flow = up_feat = xc = None
+        for lvl in (6, 5, 4, 3, 2):
+            c1, c2 = feats[0][lvl - 1], feats[1][lvl - 1]
+            if lvl == 6:
+                xc = cost_volume(c1, c2, None, 1.0)
+            else:
+                xc = torch.cat((cost_volume(c1, c2, up_flow, WARP_SCALE[lvl]), c1, up_flow, up_feat), 1)
+            convs = [getattr(self, "conv%d_%d" % (lvl, i)) for i in range(5)]
+            if self.variant == "dc":
+                for conv in convs:
+                    xc = torch.cat((conv(xc), xc), 1)
+            else:                                                            # PWCNet.py:425-429
+                xc = torch.cat((xc, convs[0](xc)), 1)
+                xc = torch.cat((convs[1](xc), xc), 1)
+                for conv in convs[2:]:
+                    xc = torch.cat((xc, conv(xc)), 1)
+            flows[lvl] = getattr(self, "predict_flow%d" % lvl)(xc)
+            if lvl > 2:
+                up_flow = getattr(self, "deconv%d" % lvl)(flows[lvl])
+                up_feat = getattr(self, "upfeat%d" % lvl)(xc)
+        t = xc
+        for i in range(1, len(CONTEXT) + 1):
+            t = getattr(self, "dc_conv%d" % i)(t)
+        flow2 = flows[2] + self.dc_conv7(t)
+        return flow2, flows[3], flows[4], flows[5], flows[6]
 
     # ---- plan management -----------------------------------------------------------------------
     def _normalize_now(self) -> bool:
