@@ -146,9 +146,13 @@ class PwcPlan:
         # per launch there.  flow[l] is then channels 0,1 of that convolution's output.
         self.head10: Dict[int, torch.Tensor] = {}
         # predict_flowL + upfeatL as one streaming pass: where its one-pass kernel runs (64 tiles) and, on Cin slices through the plan's
-        # workspace, down to "head_sliced_min_tiles" tiles (level 3 of 2..8 pairs: 20-36 us ahead of the 10-channel convolution)
-        self.stream_head = {l: conv_backend == "hip" and ops.head_upfeat_supported(
-            B, *self.size[l], min_tiles=_lib.get_option("head_sliced_min_tiles") if _lib.get_option("stream_slice_wgs") > 0 else 64)
+        # workspace, down to "head_sliced_min_tiles" tiles (level 3 of 2..8 pairs: 20-36 us ahead of the 10-channel convolution).  Below
+        # the one-pass kernel's 64 tiles the library's own slice plan decides (a workspace demand > 0 <=> it cuts the launch along Cin):
+        # with a small "stream_slice_wgs" it may not, and pwc_head_upfeat_ws_fwd would then refuse the launch
+        self.stream_head = {l: conv_backend == "hip" and (
+            ops.head_upfeat_supported(B, *self.size[l]) or (
+                ops.head_upfeat_supported(B, *self.size[l], min_tiles=_lib.get_option("head_sliced_min_tiles"))
+                and ops.head_upfeat_workspace_bytes(B, level_in_channels(l, self.nd) + DENSE_TOTAL, *self.size[l]) > 0))
             for l in range(3, 7)}
         if conv_backend == "hip" and _lib.get_option("head10"):
             for l in range(3, 7):

@@ -272,3 +272,170 @@ def test_trainable_off_paths_unchanged(dev):
     n16.load_state_dict(sd)
     with pytest.raises(NotImplementedError):
         n16.to(dev).train()(x)
+
+
+# ---- per-element bounds at the network's own channel counts and launch splits --------------------------------------------------
+# per element, against the same gradient computed from |c1|, |c2|, |gy| and |slope|: the a-priori bound n x 2^-24 of a float32 sum
+# of n terms, n ~ 90 (81 displacements + the four-tap blend + the scatter)
+REL_BWD = 6e-6
+
+
+def _taps_grads(c1, c2, flo, gy, y_gpu, scale, align, thr, normalize, absolute=False):
+    """float64 autograd of leaky(corr(c1, warp(c2))) whose tap cells, weights and mask come from the kernel's float32 sample
+    coordinates (launch_audit.warp_taps): the backward is discontinuous at cell boundaries, where float64 coordinates could send a
+    gradient to a different cell.  Returns (grad_c1, grad_c2, grad_flo); grad_flo = sum_c gw2 d w2 / d(ix, iy) d(ix, iy) / d flo
+    with the bilinear factors of the same float32 taps.  absolute: everything on |c1|, |c2|, |gy| with |slope| and |d w2 / d ix|
+    -- the sum of |terms| of each gradient."""
+    import launch_audit as LA
+    f = (lambda t: t.double().abs()) if absolute else (lambda t: t.double())
+    a, b = f(c1).requires_grad_(True), f(c2).requires_grad_(True)
+    taps = LA.warp_taps(flo, scale, align, thr) if flo is not None else None
+    w = LA.warp_apply(b, taps) if flo is not None else b
+    if flo is not None:
+        w.retain_grad()
+    x = O.correlation(a, w, 4, 1, 4, 1, 1, 1, normalize=normalize)
+    y = torch.where(y_gpu.cpu() > 0, x, 0.1 * x)
+    y.backward(f(gy))
+    if flo is None:
+        return a.grad, b.grad, None
+    x0, y0, _, _, mask, (ax1, ay1, ok) = taps
+    B, C, H, W = c2.shape
+    flat = b.detach().reshape(B, C, H * W)
+    v = []
+    for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        idx = ((y0 + dy).clamp(0, H - 1) * W + (x0 + dx).clamp(0, W - 1)).reshape(B, 1, H * W).expand(B, C, H * W)
+        v.append(torch.gather(flat, 2, idx).reshape(B, C, H, W) * (ok[k] & mask).double().unsqueeze(1))
+    ax1, ay1 = ax1.double().unsqueeze(1), ay1.double().unsqueeze(1)
+    sgn = (lambda t: t.abs()) if absolute else (lambda t: t)
+    if absolute:
+        dix = (1 - ay1) * (v[1] + v[0]) + ay1 * (v[3] + v[2])
+        diy = (1 - ax1) * (v[2] + v[0]) + ax1 * (v[3] + v[1])
+    else:
+        dix = (1 - ay1) * (v[1] - v[0]) + ay1 * (v[3] - v[2])
+        diy = (1 - ax1) * (v[2] - v[0]) + ax1 * (v[3] - v[1])
+    fx = 1.0 if align else W / max(W - 1, 1)
+    fy = 1.0 if align else H / max(H - 1, 1)
+    gw = sgn(w.grad)
+    sc = abs(scale) if absolute else scale
+    gf = torch.stack(((gw * dix).sum(1) * fx * sc, (gw * diy).sum(1) * fy * sc), 1)
+    return a.grad, b.grad, gf
+
+
+def _contributions(flo, scale, align, thr):
+    """per source element of c2: how many (pixel, tap) pairs of the scatter add into it (same count for every channel)"""
+    import launch_audit as LA
+    x0, y0, w = LA.warp_taps(flo, scale, align, thr)[:3]
+    B, _, H, W = flo.shape
+    n = torch.zeros(B, H * W, dtype=torch.float64)
+    for k, (dy, dx) in enumerate(((0, 0), (0, 1), (1, 0), (1, 1))):
+        idx = ((y0 + dy).clamp(0, H - 1) * W + (x0 + dx).clamp(0, W - 1)).reshape(B, -1)
+        n.scatter_add_(1, idx, (w[k] != 0).double().reshape(B, -1))
+    return n.view(B, 1, H, W)
+
+
+def _check_per_element(c1, c2, flo, gy, y, g1, g2, gf, scale, align, thr, normalize, what, images=None):
+    """grad_c1, grad_c2 and grad_flo per element against the float64 gradients of _taps_grads (REL_BWD x sum of |terms|; grad_c2 also
+    gets the fixed-point allowance the kernel documents: contributions x 2^-40 x M, M = 81 max|g| max|c1|).  The mask decisions are
+    the kernel's own (same float32 arithmetic), so no pixel near the threshold needs to be left out.
+    images: the images checked (every image is its own problem; the fixed-point scale M is the whole launch's).
+    Returns the worst error / bound of grad_c1 and grad_c2."""
+    import launch_audit as LA
+    c1, c2, gy = c1.cpu(), c2.cpu(), gy.cpu()
+    flo = flo.cpu() if flo is not None else None
+    cs = 1.0 / c1.shape[1] if normalize else 1.0
+    m = 81 * gy.abs().max().item() * cs * c1.abs().max().item()
+    if images is not None:
+        sel = lambda t: t[images].cpu() if t is not None else None          # noqa: E731
+        c1, c2, flo, gy, y, g1, g2, gf = (sel(t) for t in (c1, c2, flo, gy, y, g1, g2, gf))
+    r1, r2, rf = _taps_grads(c1, c2, flo, gy, y, scale, align, thr, normalize)
+    s1, s2, sf = _taps_grads(c1, c2, flo, gy, y, scale, align, thr, normalize, absolute=True)
+    allow = _contributions(flo, scale, align, thr) * 2.0 ** -40 * m if flo is not None else torch.zeros(1)
+    q1 = LA.worst(LA.bounded_ratio(g1.cpu(), r1, s1, REL_BWD))[0]
+    q2 = LA.worst(LA.bounded_ratio(g2.cpu(), r2, s2 + allow / REL_BWD, REL_BWD))[0]
+    print("%s: grad_c1 error/bound %.3f, grad_c2 %.3f" % (what, q1, q2))
+    assert q1 <= 1.0 and q2 <= 1.0, (what, q1, q2)
+    if flo is not None:
+        qf = LA.worst(LA.bounded_ratio(gf.cpu(), rf, sf, REL_BWD))[0]
+        print("%s: grad_flo error/bound %.3f" % (what, qf))
+        assert qf <= 1.0, (what, qf)
+    return q1, q2
+
+
+NET_CASES = [
+    # (id, shape, flow kind, scale, normalize)
+    ("l6-c196-tail", (4, 196, 5, 14), None, 1.0, False),        # level 6 of 320x896: 13 chunks of 16, the last of 4 channels
+    ("l5-c128", (4, 128, 10, 28), "smooth", 0.625, False),      # level 5 of train.py's shape
+    ("l4-c96", (4, 96, 20, 56), "rough", 1.25, True),           # level 4
+    ("l3-ny3-of-4", (16, 64, 56, 128), "smooth", 2.5, False),   # level 3 at batch 16, 448x1024: 448 tiles -> ny = 3 of 4 chunks
+    ("arena-views", (2, 32, 24, 64), "rough", 5.0, False),      # c1 / c2 / gy batch-strided channel slices of larger tensors
+    ("heavy-gy", (2, 32, 24, 64), "smooth", 5.0, False),        # one element of gy 1e4 x the rest
+    ("collapse", (1, 32, 16, 64), "collapse", 5.0, False),      # every pixel of an 8 x 32 tile samples one source pixel
+]
+
+
+@pytest.mark.parametrize("case", NET_CASES, ids=[c[0] for c in NET_CASES])
+def test_fused_backward_network_channel_counts_per_element(dev, case):
+    from opticalflow_amd import ops
+    cid, shape, kind, scale, normalize = case
+    B, C, H, W = shape
+    thr = THR_DC
+    if kind == "collapse":
+        c1, c2, _, gy = _inputs(shape, None, scale, False, thr, 700)
+        # pixel (x, y) of tile (tx, ty) samples (x, y) + scale * flo = the tile's centre + 0.25 (one source cell, all four taps)
+        yy, xx = torch.meshgrid(torch.arange(H, dtype=torch.float32), torch.arange(W, dtype=torch.float32), indexing="ij")
+        cx, cy = (xx // 32) * 32 + 16.25, (yy // 8) * 8 + 4.25              # sample coordinate ix = px W / (W - 1) - 0.5
+        flo = torch.stack((((cx + 0.5) * (W - 1) / W - xx) / scale, ((cy + 0.5) * (H - 1) / H - yy) / scale)).unsqueeze(0).contiguous()
+        flo = _away_from_edges(flo, scale, False, thr)
+    else:
+        c1, c2, flo, gy = _inputs(shape, kind, scale, False, thr, 700 + C)
+    if cid == "heavy-gy":
+        gy[1, 40, 11, 20] = 1e4
+    nchunk = (C + 15) // 16
+    tiles = B * ((W + 31) // 32) * ((H + 7) // 8)
+    ny = 1 if tiles >= 1024 else min((1024 + tiles - 1) // tiles, nchunk)
+    if cid == "l6-c196-tail":
+        assert nchunk == 13 and C - 16 * (nchunk - 1) == 4
+    if cid == "l3-ny3-of-4":
+        assert (tiles, ny, nchunk) == (448, 3, 4)        # one y-slice walks chunks 0 and 3: its grad_flo partials span two chunks
+    d = [t.to(dev) if t is not None else None for t in (c1, c2, flo, gy)]
+    if cid == "arena-views":
+        big = [torch.randn(B, 2 * C + 7, H, W, device=dev), torch.randn(B, 3 * C, H, W, device=dev), torch.randn(B, 170, H, W, device=dev)]
+        big[0][:, 5:5 + C] = d[0]
+        big[1][:, C:2 * C] = d[1]
+        big[2][:, 81:162] = d[3]
+        d[0], d[1], d[3] = big[0][:, 5:5 + C], big[1][:, C:2 * C], big[2][:, 81:162]
+        assert not d[0].is_contiguous() and not d[3].is_contiguous()
+    y = ops.WarpCorrelationFunction.apply(d[0], d[1], d[2], scale, False, thr, 1.0, normalize, 0.1)
+    g = ops.warp_correlation_backward(d[0], d[1], d[2], y, d[3], scale, False, thr, 1.0, normalize, 0.1)
+    _check_per_element(c1, c2, flo, gy, y, *g, scale, False, thr, normalize, cid, images=[0, 6, B - 1] if B > 4 else None)
+    h = ops.warp_correlation_backward(d[0], d[1], d[2], y, d[3], scale, False, thr, 1.0, normalize, 0.1)
+    assert all((a is None and b is None) or torch.equal(a, b) for a, b in zip(g, h))
+    k = ops.warp_correlation_backward(d[0], d[1], d[2], y, d[3], scale, False, thr, 1.0, normalize, 0.1, fused=False)
+    for a, r, n in zip(g, k, ("grad_c1", "grad_c2", "grad_flo")):
+        if a is not None:
+            _close(a, r.double().cpu(), 1e-6, n + " vs composition")
+
+
+def test_training_step_train_shape_every_cost_volume_launch(dev, monkeypatch):
+    """One training step of PWCDCNet(trainable=True) at train.py's 4 x 6 x 320 x 896: every pwc_warp_corr81_bwd launch (five levels)
+    recorded with its inputs and checked per element (_check_per_element) from those inputs, on the first and the last image."""
+    from opticalflow_amd import PWCDCNet, ops
+    net, _ = _net(PWCDCNet, dev)
+    x = seeded_rand((4, 6, 320, 896), 540).to(dev)
+    real = ops.warp_correlation_backward
+    calls = []
+
+    def spy(c1, c2, flo, y, grad_y, flow_scale=1.0, align_corners=False, mask_threshold=0.9999, corr_multiply=1.0,
+            normalize=False, leaky_slope=0.1, fused=True):
+        ins = [t.detach().cpu() if t is not None else None for t in (c1, c2, flo, y, grad_y)]
+        out = real(c1, c2, flo, y, grad_y, flow_scale, align_corners, mask_threshold, corr_multiply, normalize, leaky_slope, fused)
+        torch.cuda.synchronize()
+        calls.append((ins, [t.cpu() if t is not None else None for t in out], (flow_scale, align_corners, mask_threshold, normalize)))
+        return out
+    monkeypatch.setattr(ops, "warp_correlation_backward", spy)
+    flows = net(x)
+    sum(w * f.abs().mean() for w, f in zip(LEVEL_W, flows)).backward()
+    monkeypatch.undo()
+    assert sorted(c[0][0].shape[1] for c in calls) == [32, 64, 96, 128, 196]
+    for (c1, c2, flo, y, gy), (g1, g2, gf), (scale, align, thr, normalize) in calls:
+        _check_per_element(c1, c2, flo, gy, y, g1, g2, gf, scale, align, thr, normalize, "train step C=%d" % c1.shape[1], images=[0, 3])
