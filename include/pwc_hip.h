@@ -19,6 +19,10 @@
  *   pwc_warp_fwd        PWCDCNet.warp             models/PWCNet.py:141-177
  *   pwc_warp_bwd        autograd of the same (grid_sample backward as used by the training scripts)
  *   pwc_warp_corr81_bwd autograd of corr(c1, warp(c2, s*flo)) + LeakyReLU, PWCNet.py:212-214 etc. (train.py's loss.backward())
+ *   pwc_proxy_loss_fwd  ProxyLabelLoss.forward    train_pseudo.py:65-164, train_fundamental.py:62-166 (photometric SSIM + L1
+ *                       of the flow-warped image, first-order smoothness)
+ *   pwc_proxy_loss_bwd  autograd of the same w.r.t. the flow (train_pseudo's / train_fundamental's loss.backward())
+ *   pwc_flow_warp_image_fwd  ProxyLabelLoss.warp  train_pseudo.py:122-157, warp_image train_fundamental.py:80-99
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -159,6 +163,52 @@ int pwc_warp_corr81_bwd(const void *c1, const void *c2, const void *flo, const v
                         unsigned flags, float leaky_slope,
                         int64_t c1_bstride, int64_t c2_bstride, int64_t flo_bstride, int64_t y_bstride, int64_t gy_bstride,
                         void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Self-supervised proxy-label loss (ABI v13 additions, csrc/pwc_proxy_loss.hip), restating train_pseudo.py:65-164 (ssim_eps 0) and
+ * train_fundamental.py:62-166 (ssim_eps 1e-12, optional valid_mask):
+ *   up     = interpolate(flow, (H,W), bilinear, align_corners=True) * (W/w, H/h)   (flow itself when (h,w) == (H,W));
+ *   y_c    = grid_sample(img2, x + up, bilinear, border, align_corners=True)         (train_pseudo.py:122-157, :80-99);
+ *   map    = 0.85 mean_c clamp((1 - SSIM_c(img1, y)) / 2, 0, 1) + 0.15 mean_c |img1 - y|, SSIM on avg_pool2d(3, 1, 1)
+ *            (zero padding, divisor 9) moments with C1 = 0.01^2, C2 = 0.03^2 and + ssim_eps in the denominator (:87-101, :139-150);
+ *   photo  = mean(map), or with a mask sum(map * [m > 0.5]) / max(sum [m > 0.5], 1) (:117-126);
+ *   smooth = mean|d/dx flow| + mean|d/dy flow| on the low-resolution flow (:103-107, :152-156);
+ *   total  = alpha_photo * photo + alpha_smooth * smooth.
+ * flow [B,2,h,w], img1 / img2 [B,C,H,W] f32 (dense C,H,W planes, batch strides in elements); mask [B,H,W] (plane dense, batch
+ * stride mask_bstride) stored as f32 (mask_u8 = 0) or u8 (mask_u8 = 1), or NULL.  The sample point is computed in fp32 as
+ *   rh = (float)(h-1) / (float)(H-1);  fy = rh * (float)Y;  y0 = (int)fy;  y1 = y0 + (y0 < h-1);  ly1 = fy - (float)y0;  ly0 = 1 - ly1
+ *   (x alike);  up_x = (ly0 * (lx0 * f00 + lx1 * f01) + ly1 * (lx0 * f10 + lx1 * f11)) * (float)((double)W / w)  (v alike with H / h);
+ *   px = (float)X + up_x;  ix = min(max(px, 0), W-1);  x0 = floor(ix);  tx = ix - x0   (y alike)
+ * with no fused multiply-add (the library is built with -ffp-contract=off); the reference's linspace + normalise + unnormalise
+ * chain computes the same point in exact arithmetic.
+ * pwc_proxy_loss_fwd writes float out[3] = {total, photo, smooth} in device memory; partial sums per 16 x 64 tile in fp64, added in
+ * a fixed order.  pwc_proxy_loss_bwd reads grad_out[3] = {g_total, g_photo, g_smooth} from device memory (no host sync) and writes
+ * grad_flow [B,2,h,w] (dense) = (g_total * alpha_photo + g_photo) d photo / d flow + (g_total * alpha_smooth + g_smooth) d smooth / d flow,
+ * the gradient autograd derives from the reference's expression: 0 where a sample coordinate is clipped (<= 0 or >= size-1),
+ * clamp passes on its closed interval, |0| has gradient 0; the images and the mask get none.  It recomputes the warp and the
+ * moments per tile (nothing is kept from the forward) and gathers grad_flow in a fixed order: both entries are bit-reproducible.
+ * workspace: device, 8-byte aligned; the forward needs pwc_proxy_loss_fwd_workspace_bytes (32 bytes per 16 x 64 tile), the backward
+ * pwc_proxy_loss_workspace_bytes (grad_up [B,2,H,W] + 256 bytes; also >= the forward's, so one buffer serves both entries).
+ * The backward's gather gives one lane per low-resolution pixel about (2H/h) x (2W/w) full-resolution pixels to sum: fine at the
+ * scripts' 4x upsampling, slow (correct) at extreme ratios such as a 2 x 2 flow.
+ * Null operands (mask excepted) / bad shapes / short strides / short workspace: PWC_EINVAL before any launch.
+ * PWC_EUNSUPPORTED (nothing launched) when H, W, h or w < 2, H < h, W < w, an f32 operand is not 4-byte aligned, C*H*W >= 2^31,
+ * B > 65535 or H > 16 * 65535. */
+int64_t pwc_proxy_loss_workspace_bytes(int B, int C, int H, int W, int h, int w);
+int64_t pwc_proxy_loss_fwd_workspace_bytes(int B, int C, int H, int W, int h, int w);
+int pwc_proxy_loss_fwd(const void *flow, const void *img1, const void *img2, const void *mask, int mask_u8,
+                       void *out, int B, int C, int H, int W, int h, int w,
+                       float alpha_photo, float alpha_smooth, float ssim_eps,
+                       int64_t flow_bstride, int64_t img1_bstride, int64_t img2_bstride, int64_t mask_bstride,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+int pwc_proxy_loss_bwd(const void *flow, const void *img1, const void *img2, const void *mask, int mask_u8,
+                       const void *grad_out, void *grad_flow, int B, int C, int H, int W, int h, int w,
+                       float alpha_photo, float alpha_smooth, float ssim_eps,
+                       int64_t flow_bstride, int64_t img1_bstride, int64_t img2_bstride, int64_t mask_bstride,
+                       void *workspace, int64_t workspace_bytes, void *stream);
+/* warp / warp_image of the same scripts (train_pseudo.py:122-157, train_fundamental.py:80-99), forward only, any C:
+ * out [B,C,H,W] = img sampled at the point above (flow [B,2,h,w], upsampled when (h,w) != (H,W)).  Same declines as the loss. */
+int pwc_flow_warp_image_fwd(const void *img, const void *flow, void *out, int B, int C, int H, int W, int h, int w,
+                            int64_t img_bstride, int64_t flow_bstride, int64_t out_bstride, void *stream);
 
 /* Backward warp of x by (flow_scale * flo): bilinear, zero padding, times the validity mask
  * [sum of in-bounds bilinear weights >= mask_threshold]  (PWCNet.py:141-177).

@@ -46,6 +46,13 @@ SIGNATURES = {
     "pwc_warp_corr81_bwd_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "pwc_warp_corr81_bwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_int, c_int, c_float, c_int, c_float, c_float, c_uint, c_float]
                             + [c_int64] * 5 + [c_void_p, c_int64, c_void_p]),
+    "pwc_proxy_loss_workspace_bytes": (c_int64, [c_int] * 6),
+    "pwc_proxy_loss_fwd_workspace_bytes": (c_int64, [c_int] * 6),
+    "pwc_proxy_loss_fwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p] + [c_int] * 6 + [c_float] * 3 + [c_int64] * 4
+                           + [c_void_p, c_int64, c_void_p]),
+    "pwc_proxy_loss_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_float] * 3 + [c_int64] * 4
+                           + [c_void_p, c_int64, c_void_p]),
+    "pwc_flow_warp_image_fwd": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_int64] * 3 + [c_void_p]),
     "pwc_conv3x3_packed_bytes": (c_int64, [c_int, c_int, c_int]),
     "pwc_conv3x3_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "pwc_conv2d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

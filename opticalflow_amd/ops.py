@@ -647,3 +647,139 @@ def deconv4x4s2(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor,
                                      B, cin, H, W, cout, _dtype_code(x), bsx, bsy, _stream(x))
     check(rc, "pwc_deconv4x4s2_fwd")
     return out
+
+
+# ---------------------------------------------------------------- self-supervised proxy-label loss (train_pseudo / train_fundamental)
+def proxy_loss_supported(flow: torch.Tensor, img1: torch.Tensor, img2: torch.Tensor, mask: Optional[torch.Tensor] = None) -> bool:
+    """Python mirror of the geometry / placement rules under which pwc_proxy_loss_fwd / _bwd launch (include/pwc_hip.h):
+    ROCm device tensors, f32 after the cast, 2 <= h <= H, 2 <= w <= W, C*H*W < 2^31, B <= 65535."""
+    if not (flow.is_cuda and img1.is_cuda and img2.is_cuda) or (mask is not None and not mask.is_cuda):
+        return False
+    if flow.dim() != 4 or img1.dim() != 4 or flow.shape[1] != 2 or img1.shape != img2.shape or flow.shape[0] != img1.shape[0]:
+        return False
+    B, C, H, W = img1.shape
+    h, w = flow.shape[-2:]
+    return 2 <= h <= H and 2 <= w <= W and C * H * W < 2 ** 31 and 1 <= B <= 65535 and (H + 15) // 16 <= 65535
+
+
+def proxy_loss_workspace_bytes(B: int, C: int, H: int, W: int, h: int, w: int, forward_only: bool = False) -> int:
+    """Scratch bytes of pwc_proxy_loss_bwd (enough for the forward too), or of pwc_proxy_loss_fwd alone with forward_only."""
+    lib = _lib.load()
+    fn = lib.pwc_proxy_loss_fwd_workspace_bytes if forward_only else lib.pwc_proxy_loss_workspace_bytes
+    n = fn(B, C, H, W, h, w)
+    if n < 0:
+        raise ValueError("bad proxy-loss geometry")
+    return int(n)
+
+
+def _mask_arg(mask: Optional[torch.Tensor], B: int, H: int, W: int) -> Tuple[Optional[torch.Tensor], int, int]:
+    """[B,H,W] / [B,1,H,W] mask as the kernels read it: (tensor, mask_u8, batch stride).  bool -> its bytes; float32 as is;
+    any other dtype -> (mask > 0.5) as bytes (the same decision the kernels take on f32)."""
+    if mask is None:
+        return None, 0, 0
+    if mask.dim() == 4:
+        mask = mask[:, 0]
+    if tuple(mask.shape) != (B, H, W):
+        raise ValueError("valid_mask must be [B,H,W] or [B,1,H,W] = %s, got %s" % ((B, H, W), tuple(mask.shape)))
+    if mask.dtype == torch.bool:
+        m, u8 = mask.contiguous().view(torch.uint8), 1
+    elif mask.dtype == torch.float32:
+        m, u8 = mask.contiguous(), 0
+    elif mask.dtype == torch.uint8:
+        m, u8 = mask.contiguous(), 1
+    else:
+        m, u8 = (mask > 0.5).contiguous().view(torch.uint8), 1
+    return m, u8, H * W
+
+
+def _proxy_args(flow, img1, img2, mask):
+    flow, img1, img2 = densify(flow), densify(img1), densify(img2)
+    B, C, H, W = img1.shape
+    h, w = flow.shape[-2:]
+    for name, t, shp in (("flow", flow, (B, 2, h, w)), ("img1", img1, (B, C, H, W)), ("img2", img2, (B, C, H, W))):
+        if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != img1.device:
+            raise ValueError("%s must be float32 %s on %s, got %s %s" % (name, shp, img1.device, t.dtype, tuple(t.shape)))
+    m, u8, bsm = _mask_arg(mask, B, H, W)
+    if m is not None and m.device != img1.device:
+        raise ValueError("valid_mask must be on %s" % img1.device)
+    bs = (_plane_dense(flow, "flow"), _plane_dense(img1, "img1"), _plane_dense(img2, "img2"))
+    return flow, img1, img2, m, u8, bsm, bs, (B, C, H, W, h, w)
+
+
+def _proxy_workspace(dims, device, forward_only=False) -> Tuple[torch.Tensor, int]:
+    nb = proxy_loss_workspace_bytes(*dims, forward_only=forward_only)
+    return torch.empty((nb + 7) // 8, dtype=torch.int64, device=device), nb
+
+
+def proxy_loss(flow: torch.Tensor, img1: torch.Tensor, img2: torch.Tensor, mask: Optional[torch.Tensor] = None,
+               alpha_photo: float = 1.0, alpha_smooth: float = 0.1, ssim_eps: float = 0.0) -> torch.Tensor:
+    """float32 [3] = (total, photo, smooth) of the proxy-label loss (pwc_proxy_loss_fwd; train_pseudo.py:65-164 with ssim_eps 0,
+    train_fundamental.py:62-166 with 1e-12 and an optional [B,H,W] / [B,1,H,W] mask).  No host synchronisation."""
+    lib = _lib.load()
+    flow, img1, img2, m, u8, bsm, bs, dims = _proxy_args(flow, img1, img2, mask)
+    out = torch.empty(3, dtype=torch.float32, device=img1.device)
+    with torch.cuda.device(img1.device):
+        ws, nb = _proxy_workspace(dims, img1.device, forward_only=True)
+        rc = lib.pwc_proxy_loss_fwd(flow.data_ptr(), img1.data_ptr(), img2.data_ptr(), m.data_ptr() if m is not None else None, u8,
+                                    out.data_ptr(), *dims, float(alpha_photo), float(alpha_smooth), float(ssim_eps),
+                                    bs[0], bs[1], bs[2], bsm, ws.data_ptr(), nb, _stream(img1))
+    check(rc, "pwc_proxy_loss_fwd")
+    return out
+
+
+def proxy_loss_backward(flow: torch.Tensor, img1: torch.Tensor, img2: torch.Tensor, mask: Optional[torch.Tensor],
+                        grad_out: torch.Tensor, alpha_photo: float = 1.0, alpha_smooth: float = 0.1,
+                        ssim_eps: float = 0.0) -> torch.Tensor:
+    """grad_flow [B,2,h,w] of the proxy-label loss for upstream gradients grad_out = (g_total, g_photo, g_smooth), a float32 [3]
+    device tensor (pwc_proxy_loss_bwd: recomputes, deterministic, no host synchronisation)."""
+    lib = _lib.load()
+    flow, img1, img2, m, u8, bsm, bs, dims = _proxy_args(flow, img1, img2, mask)
+    g = grad_out.to(device=img1.device, dtype=torch.float32).contiguous().reshape(3)
+    B, _, _, _, h, w = dims
+    gf = torch.empty((B, 2, h, w), dtype=torch.float32, device=img1.device)
+    with torch.cuda.device(img1.device):
+        ws, nb = _proxy_workspace(dims, img1.device)
+        rc = lib.pwc_proxy_loss_bwd(flow.data_ptr(), img1.data_ptr(), img2.data_ptr(), m.data_ptr() if m is not None else None, u8,
+                                    g.data_ptr(), gf.data_ptr(), *dims, float(alpha_photo), float(alpha_smooth), float(ssim_eps),
+                                    bs[0], bs[1], bs[2], bsm, ws.data_ptr(), nb, _stream(img1))
+    check(rc, "pwc_proxy_loss_bwd")
+    return gf
+
+
+def flow_warp_image(img: torch.Tensor, flow: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """warp / warp_image of train_pseudo.py:122-157 / train_fundamental.py:80-99 (forward only, any C): img [B,C,H,W] sampled at
+    x + upsample(flow) (bilinear, border, align_corners=True); flow [B,2,h,w] with 2 <= h <= H, 2 <= w <= W."""
+    lib = _lib.load()
+    img, flow = densify(img), densify(flow)
+    B, C, H, W = img.shape
+    h, w = flow.shape[-2:]
+    if tuple(flow.shape) != (B, 2, h, w) or img.dtype != torch.float32 or flow.dtype != torch.float32 or flow.device != img.device:
+        raise ValueError("img must be float32 [B,C,H,W] and flow float32 [B,2,h,w] on one device")
+    if out is None:
+        out = torch.empty_like(img, memory_format=torch.contiguous_format)
+    bsi, bsf, bso = _plane_dense(img, "img"), _plane_dense(flow, "flow"), _plane_dense(out, "out")
+    with torch.cuda.device(img.device):
+        rc = lib.pwc_flow_warp_image_fwd(img.data_ptr(), flow.data_ptr(), out.data_ptr(), B, C, H, W, h, w, bsi, bsf, bso, _stream(img))
+    check(rc, "pwc_flow_warp_image_fwd")
+    return out
+
+
+class ProxyLossFunction(torch.autograd.Function):
+    """autograd of the proxy-label loss w.r.t. the flow: forward pwc_proxy_loss_fwd, backward pwc_proxy_loss_bwd (recomputes from
+    the inputs; nothing image-sized is saved beyond the inputs themselves).  Returns a float32 [3] tensor (total, photo, smooth).
+    Under torch.autocast the inputs are cast to float32.  apply(flow, img1, img2, mask, alpha_photo, alpha_smooth, ssim_eps);
+    img1, img2 and mask get no gradient (callers route images that require grad to the torch composition)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, flow, img1, img2, mask=None, alpha_photo=1.0, alpha_smooth=0.1, ssim_eps=0.0):
+        ctx.save_for_backward(flow, img1, img2, mask)
+        ctx.cfg = (float(alpha_photo), float(alpha_smooth), float(ssim_eps))
+        return proxy_loss(flow, img1, img2, mask, *ctx.cfg)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        flow, img1, img2, mask = ctx.saved_tensors
+        gf = proxy_loss_backward(flow, img1, img2, mask, grad_out, *ctx.cfg)
+        return gf, None, None, None, None, None, None
