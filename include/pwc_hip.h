@@ -95,7 +95,10 @@ const char *pwc_last_error(void);
  *   upfeatL through pwc_head_upfeat_ws_fwd -- on Cin slices below the 64 tiles its one-pass form needs -- instead of the 10-channel
  *   convolution of "head10"; 64: only where the one-pass kernel runs),
  *   "c1_in_arena" [PWC_C1_IN_ARENA] 1 (fp32 plans: the level features of both images live at the arena's batch stride, so that the pyramid's
- *   last convolution writes the first image's straight into their arena slot; 0: dense pyramid buffers and one copy per level).
+ *   last convolution writes the first image's straight into their arena slot; 0: dense pyramid buffers and one copy per level),
+ *   "w4_stacked" [PWC_W4_STACKED] 1 (pwc_conv3x3_wino4_preferred takes maps shorter than an F(4x4) workgroup where a stacked form -- several
+ *   images per workgroup, each with its own border -- serves them: 14x32 for a 32-cout launch, 7x16 for a 64-cout one; the fp32 plan then
+ *   runs dc_conv4 / dc_conv5 on the level-4 lattices; 0: refused, the round-4 context path).
  * Unknown name: PWC_EINVAL.  A captured HIP graph keeps the kernels chosen at capture time. */
 int pwc_set_option(const char *name, int value);
 int pwc_get_option(const char *name, int *value);

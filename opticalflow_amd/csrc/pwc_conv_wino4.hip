@@ -43,21 +43,29 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 constexpr int kThreads = 512;
 constexpr int kCK = 4;               // input channels per chunk = K of one MFMA
 // A tile group is sixteen 4x4 tiles: one row of 16 (GW = 64 output columns x 4 rows) or, for narrow maps (the 14x32 lattice images of
-// dc_conv4), two rows of 8 (GW = 32 columns x 8 rows).  A staged row holds global columns ox0 - 4 .. ox0 + GW + 3 as 16-byte pieces and
-// lands ONE float to the right of a 16-byte LDS boundary, so that global column ox0 - 1 (the first patch column) sits at index 4:
-// every patch row is 16-byte aligned.
+// dc_conv4), two rows of 8 (GW = 32 columns x 8 rows), or four rows of 4 (GW = 16 x 16 rows: only stacked, see IH).  A staged row holds
+// global columns ox0 - 4 .. ox0 + GW + 3 as 16-byte pieces and lands ONE float to the right of a 16-byte LDS boundary, so that global
+// column ox0 - 1 (the first patch column) sits at index 4: every patch row is 16-byte aligned.
+// STACKED form (IH > 0), for maps shorter than the workgroup's kGH * TG rows (the 14x32 and 7x16 lattice images of dc_conv4 / dc_conv5):
+// the workgroup's rows are kImg = kGH TG / IH consecutive images of the batch, each padded to IH = ceil(H / 4) * 4 rows.  Every image is
+// staged as its own block of IH + 2 rows, zero top and bottom border included, and a tile's patch never leaves its image's block -- so
+// an image's result does not depend on its neighbours in the batch, nor on its place in the group.
 constexpr unsigned kOOB = 0x80000000u;
 
-template <int CB, int TG, int GW = 64>
+template <int CB, int TG, int GW = 64, int IH = 0>
 struct Geo4 {
     static_assert(CB * TG == 8, "eight waves");
-    static_assert(GW == 64 || GW == 32, "tile-group width");
+    static_assert(GW == 64 || GW == 32 || (GW == 16 && IH > 0), "tile-group width");
     static constexpr int kGW = GW;
-    static constexpr int kTC = GW / 4;                                // tiles per tile row of a group (16 or 8)
-    static constexpr int kGH = 4 * (16 / kTC);                        // output rows of a group (4 or 8)
-    static constexpr int kRowP = (GW + 8) / 4;                        // 16-byte pieces per staged row (18 or 10)
-    static constexpr int kRawW = 4 * kRowP;                           // 72 or 40 floats
-    static constexpr int kRows = kGH * TG + 2;
+    static constexpr int kTC = GW / 4;                                // tiles per tile row of a group (16, 8 or 4)
+    static constexpr int kGH = 4 * (16 / kTC);                        // output rows of a group (4, 8 or 16)
+    static constexpr int kTH = kGH * TG;                              // output rows of a workgroup
+    static constexpr int kIH = IH ? IH : kTH;                         // rows of one image block (padded image height when stacked)
+    static constexpr int kImg = kTH / kIH;                            // images per workgroup
+    static_assert(IH % 4 == 0 && kTH % kIH == 0 && (IH == 0 || kImg >= 2), "whole 4-row tiles per image, whole images per workgroup");
+    static constexpr int kRowP = (GW + 8) / 4;                        // 16-byte pieces per staged row (18, 10 or 6)
+    static constexpr int kRawW = 4 * kRowP;                           // 72, 40 or 24 floats
+    static constexpr int kRows = kImg * (kIH + 2);                    // staged rows: every image block with its two border rows
     static constexpr int kPP = (kRows * kRowP + 15) / 16 * 16;        // pieces per staged channel, padded: planes are multiples of 64 floats
     static constexpr int kPlane = 4 * kPP;
     static constexpr int kRawPieces = kCK * kPP;
@@ -153,7 +161,7 @@ wino4_pack_kernel(const float *__restrict__ w, float *__restrict__ up, int Cin, 
 #define PWC_WAIT_VMCNT(n) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(n) : "memory")
 
 // Split of a launch's LAST, partial round of workgroups along the input channels (see launch_wino4).  ksplit <= 1: an ordinary launch
-// over the given tile positions of every image.
+// over the given tile positions of every image.  In the stacked form an "image" here is a group of Geo4::kImg images.
 struct TailSplit {
     int per_image;    // tiles of ONE image that belong to this launch: positions pos0 .. pos0 + per_image - 1 of its tiles_x * tiles_y tiles --
     int pos0;         // the same positions of every image, so that an item's result does not depend on its slot in the batch
@@ -191,12 +199,12 @@ __device__ __forceinline__ void bt3_row(const float (&d)[6], float (&t)[3]) {   
     asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]));
 }
 
-template <int CB, int TG, int GW, int HJ>
+template <int CB, int TG, int GW, int IH, int HJ>
 __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
-                                            float *__restrict__ y, int Cin_all, int H, int W, int Cout, int CoutP, int tiles_x, int tiles_y,
+                                            float *__restrict__ y, int B, int Cin_all, int H, int W, int Cout, int CoutP, int tiles_x, int tiles_y,
                                             int64_t bsx, int64_t bsy, float slope, int do_leaky, int co0, int nblk, int ngroups, int split2,
                                             const TailSplit ts) {
-    using G = Geo4<CB, TG, GW>;
+    using G = Geo4<CB, TG, GW, IH>;
     constexpr int kRowP = G::kRowP, kRawW = G::kRawW;
     extern __shared__ __attribute__((aligned(16))) float smem[];      // 3 x [raw | U]
 
@@ -230,14 +238,15 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
         }
     }
     const int tail_tile = bid;                                  // index inside this launch (the workspace is laid out by it)
-    const int b = bid / ts.per_image;
+    const int b = bid / ts.per_image;                           // image, or group of kImg images (stacked form: first image b * kImg)
     const int pos = ts.pos0 + bid % ts.per_image;
     const int tx = pos % tiles_x;
     const int ty = pos / tiles_x;
     const int cb0 = co0 + grp * G::kCoutT;
     const int ox0 = tx * G::kGW;
-    const int oy0 = ty * (G::kGH * TG);
+    const int oy0 = ty * G::kTH;
     const int plane = H * W;
+    const int nimg = IH ? min(G::kImg, B - b * G::kImg) : 1;      // images of this workgroup that exist (stacked: the last group may be short)
 
     // ---- per-lane LDS-DMA source offsets -------------------------------------------------------------
     // waves are numbered so that the raw and the U tails are issued by the first kRawWaves / kUWaves waves
@@ -248,10 +257,16 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
         const int c = i / G::kPP;
         const int rem = i % G::kPP;
         const int row = rem / kRowP, q = rem % kRowP;
-        const int iy = oy0 - 1 + row;
         const int ix = ox0 - 4 + 4 * q;                   // W % 4 == 0: a piece is all-in or all-out
-        const bool ok = (i < G::kRawPieces) && (row < G::kRows) && (iy >= 0) && (iy < H) && (ix >= 0) && (ix < W);
-        raw_off[j] = ok ? (unsigned)(c * plane + iy * W + ix) * 4u : kOOB;
+        if constexpr (IH == 0) {
+            const int iy = oy0 - 1 + row;
+            const bool ok = (i < G::kRawPieces) && (row < G::kRows) && (iy >= 0) && (iy < H) && (ix >= 0) && (ix < W);
+            raw_off[j] = ok ? (unsigned)(c * plane + iy * W + ix) * 4u : kOOB;
+        } else {                                          // row of image block m: image row iy of image b kImg + m (oy0 = 0)
+            const int m = row / (IH + 2), iy = row % (IH + 2) - 1;
+            const bool ok = (i < G::kRawPieces) && (row < G::kRows) && (m < nimg) && (iy >= 0) && (iy < H) && (ix >= 0) && (ix < W);
+            raw_off[j] = ok ? (unsigned)((int64_t)m * bsx + c * plane + iy * W + ix) * 4u : kOOB;
+        }
     }
     // U piece p = j * kThreads + tid = (row r = p / CoutT of the [36][CoutT] image, cout c): instruction j reads rows kThreads / CoutT
     // further down -> one per-lane offset + a wave-uniform byte offset per instruction
@@ -263,7 +278,10 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
     const int k_lo = kz * ts.cps, k_hi = ts.ksplit > 1 ? min((Cin_all + kCK - 1) / kCK, k_lo + ts.cps) : (Cin_all + kCK - 1) / kCK;
     const int Cin = min(Cin_all, k_hi * kCK) - k_lo * kCK;
     const int nchunks = k_hi - k_lo;
-    const float *xb = x + (int64_t)b * bsx + (int64_t)k_lo * kCK * plane;
+    const float *xb = x + (int64_t)b * G::kImg * bsx + (int64_t)k_lo * kCK * plane;
+    // bytes before a chunk's first channel of the group's LAST image (0 unless stacked: the launcher checks that it fits 31 bits, and
+    // that Cin % 4 == 0, so that no chunk is ragged -- the range check cannot cut channels out of the middle of the group)
+    const int ispan = IH ? (int)((int64_t)(nimg - 1) * bsx * 4) : 0;
     const float *ug = up + (int64_t)cb0 * 4 + (int64_t)k_lo * uchunk;
     const int ubytes = (int)(uchunk - (int64_t)cb0 * 4) * 4;
     const unsigned lds0 = pwc::lds_addr(smem);
@@ -272,7 +290,8 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
         // a chunk past the end gets a zero-sized descriptor: every lane fails the range check, nothing is fetched, zeros land in a slot
         // nobody reads -- so EVERY iteration issues a whole group and the counted waits never change
         const int c0 = (PWC_W4_EXP & 2) ? 0 : chunk * kCK;
-        const pwc::v4i32 rs = pwc::make_rsrc(xb + (int64_t)min(c0, Cin - 1) * plane, max(0, min(kCK, Cin - c0)) * plane * 4);
+        const int nb = max(0, min(kCK, Cin - c0)) * plane * 4;
+        const pwc::v4i32 rs = pwc::make_rsrc(xb + (int64_t)min(c0, Cin - 1) * plane, nb ? nb + ispan : 0);
         const unsigned base = __builtin_amdgcn_readfirstlane(lds0 + (chunk % 3) * G::kSlot * 4 + 4 + wave * 1024);
 #pragma unroll
         for (int j = 0; j < G::kRS; ++j)
@@ -290,7 +309,8 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
     unsigned base_r = 0, base_u = 0;
     auto setup_dma = [&](int k) {
         const int c0 = (k + 3) * kCK;
-        rs_r = pwc::make_rsrc(xb + (int64_t)min(c0, Cin - 1) * plane, max(0, min(kCK, Cin - c0)) * plane * 4);
+        const int nb = max(0, min(kCK, Cin - c0)) * plane * 4;
+        rs_r = pwc::make_rsrc(xb + (int64_t)min(c0, Cin - 1) * plane, nb ? nb + ispan : 0);
         base_r = __builtin_amdgcn_readfirstlane(lds0 + ((k + 3) % 3) * G::kSlot * 4 + 4 + wave * 1024);
         rs_u = pwc::make_rsrc(ug + (int64_t)min(k + 2, nchunks - 1) * uchunk, k + 2 < nchunks ? ubytes : 0);
         base_u = __builtin_amdgcn_readfirstlane(lds0 + (((k + 2) % 3) * G::kSlot + G::kRawFloats) * 4 + wave * 1024);
@@ -315,8 +335,10 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
 
 
     // this lane's tile inside its group: tile row n / kTC, tile column n % kTC; its patch inside a raw slot: channel kq, rows
-    // GH tgi + 4 tr .. + 5, columns 4 tc .. 4 tc + 5 (+ 4: the row lands one float to the right of a 16-byte boundary)
-    const int poff = kq * G::kPlane + (G::kGH * tgi + 4 * (n / G::kTC)) * kRawW + 4 + 4 * (n % G::kTC);
+    // vr .. vr + 5 of its image block (vr = GH tgi + 4 tr inside the workgroup), columns 4 tc .. 4 tc + 5 (+ 4: the row lands one float
+    // to the right of a 16-byte boundary)
+    const int vr = G::kGH * tgi + 4 * (n / G::kTC);
+    const int poff = kq * G::kPlane + ((vr / G::kIH) * (G::kIH + 2) + vr % G::kIH) * kRawW + 4 + 4 * (n % G::kTC);
     // this lane's U column inside a slot's U image: [g][k = kq][cout = 32 cg2 + 16 cbl + n][4]
     const int uoff = G::kRawFloats + (kq * G::kCoutT + 32 * cg2 + n) * 4;
     constexpr int kUG = kCK * G::kCoutT * 4;              // floats per position group g
@@ -485,7 +507,9 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
         }
     }
     __syncthreads();
-    const int oyl = oy0 + G::kGH * tgi + 4 * ((lane_e & 15) / G::kTC), ox = ox0 + 4 * ((lane_e & 15) % G::kTC);
+    const int vre = G::kGH * tgi + 4 * ((lane_e & 15) / G::kTC), ox = ox0 + 4 * ((lane_e & 15) % G::kTC);  // this lane's tile, rows in the workgroup
+    const int bo = IH ? b * G::kImg + vre / G::kIH : b;         // its image
+    const int oyl = IH ? vre % G::kIH : oy0 + vre;              // its first row in that image
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         const int co = cb0 + 32 * cg2 + 16 * HJ + 4 * (lane_e >> 4) + c;
@@ -502,13 +526,13 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
             if (ts.ksplit > 1) {
                 // raw partial sums of slice kz: workspace [slice][tile of the tail][cout of the layer][tile rows][tile columns]
                 if (co < Cout)
-                    *reinterpret_cast<f32x4 *>(ts.ws + ((((int64_t)kz * nblk + tail_tile) * Cout + co) * (G::kGH * TG) + (oy - oy0)) * G::kGW + (ox - ox0)) =
+                    *reinterpret_cast<f32x4 *>(ts.ws + ((((int64_t)kz * nblk + tail_tile) * Cout + co) * G::kTH + vre + pp) * G::kGW + (ox - ox0)) =
                         (f32x4){o[0], o[1], o[2], o[3]};
-            } else if (co < Cout && oy < H && ox < W) {
+            } else if (co < Cout && oy < H && ox < W && (IH == 0 || bo < B)) {
                 if (!split2) {
-                    *reinterpret_cast<f32x4 *>(y + (int64_t)b * bsy + (int64_t)co * plane + (int64_t)oy * W + ox) = (f32x4){o[0], o[1], o[2], o[3]};
+                    *reinterpret_cast<f32x4 *>(y + (int64_t)bo * bsy + (int64_t)co * plane + (int64_t)oy * W + ox) = (f32x4){o[0], o[1], o[2], o[3]};
                 } else {
-                    float *d0 = y + ((int64_t)b * 4 + 2 * (oy & 1)) * bsy + (int64_t)co * (plane >> 2) + (int64_t)(oy >> 1) * (W >> 1) + (ox >> 1);
+                    float *d0 = y + ((int64_t)bo * 4 + 2 * (oy & 1)) * bsy + (int64_t)co * (plane >> 2) + (int64_t)(oy >> 1) * (W >> 1) + (ox >> 1);
                     *reinterpret_cast<f32x2 *>(d0) = (f32x2){o[0], o[2]};
                     *reinterpret_cast<f32x2 *>(d0 + bsy) = (f32x2){o[1], o[3]};
                 }
@@ -517,23 +541,24 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
     }
 }
 
-template <int CB, int TG, int GW>
+template <int CB, int TG, int GW, int IH>
 __global__ void __launch_bounds__(kThreads, 1)
 conv3x3_wino4p_kernel(const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
-                      float *__restrict__ y, int Cin, int H, int W, int Cout, int CoutP, int tiles_x, int tiles_y,
+                      float *__restrict__ y, int B, int Cin, int H, int W, int Cout, int CoutP, int tiles_x, int tiles_y,
                       int64_t bsx, int64_t bsy, float slope, int do_leaky, int co0, int nblk, int ngroups, int split2, const TailSplit ts) {
     // the position half is wave-uniform: two specialisations of the body, every index inside is a compile-time constant
     if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 1)
-        wino4p_body<CB, TG, GW, 1>(x, up, bias, y, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, nblk, ngroups, split2, ts);
+        wino4p_body<CB, TG, GW, IH, 1>(x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, nblk, ngroups, split2, ts);
     else
-        wino4p_body<CB, TG, GW, 0>(x, up, bias, y, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, nblk, ngroups, split2, ts);
+        wino4p_body<CB, TG, GW, IH, 0>(x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, nblk, ngroups, split2, ts);
 }
 
 // Finishes the tiles of a tail launch: y = act(bias + sum over slices, in slice order (deterministic)) for couts co0 .. co0 + ncout - 1
-// of the ntail tiles of the tail launch; one thread per four pixels of a tile row.
+// of the ntail tiles of the tail launch; one thread per four pixels of a tile row.  ih > 0: the stacked form, a tile's th rows are
+// th / ih images of ih rows (B images in all).
 __global__ void __launch_bounds__(256)
 wino4_tail_reduce_kernel(const float *__restrict__ ws, const float *__restrict__ bias, float *__restrict__ y, int ksplit, int per_image, int pos0,
-                         int ntail, int tiles_x, int th, int tw, int H, int W, int Cout, int co0, int ncout, int64_t bsy, float slope,
+                         int ntail, int tiles_x, int th, int tw, int ih, int B, int H, int W, int Cout, int co0, int ncout, int64_t bsy, float slope,
                          int do_leaky, int split2, int64_t total) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
@@ -544,10 +569,11 @@ wino4_tail_reduce_kernel(const float *__restrict__ ws, const float *__restrict__
     t /= th;
     const int co = co0 + (int)(t % ncout);
     const int tt = (int)(t / ncout);
-    const int b = tt / per_image, pos = pos0 + tt % per_image;
+    const int g = tt / per_image, pos = pos0 + tt % per_image;
     const int tx = pos % tiles_x, ty = pos / tiles_x;
-    const int oy = ty * th + r, ox = tx * tw + 4 * xq;
-    if (co >= Cout || oy >= H || ox >= W) return;
+    const int b = ih ? g * (th / ih) + r / ih : g;
+    const int oy = ih ? r % ih : ty * th + r, ox = tx * tw + 4 * xq;
+    if (co >= Cout || oy >= H || ox >= W || b >= B) return;
     const int64_t slice = (int64_t)ntail * Cout * th * tw;
     const float *p = ws + (((int64_t)tt * Cout + co) * th + r) * tw + 4 * xq;
     f32x4 v = *reinterpret_cast<const f32x4 *>(p);
@@ -660,38 +686,43 @@ inline TailPlan wino4_tail_plan(int B, int64_t nblk, int ngroups, int nchunks, i
     return p;
 }
 
-template <int CB, int TG, int GW>
+template <int CB, int TG, int GW, int IH = 0>
 int launch_wino4(const float *x, const float *up, const float *bias, float *y, int B, int Cin, int H, int W, int Cout,
                  int64_t bsx, int64_t bsy, float slope, int do_leaky, hipStream_t st, int co0, int ngroups, int split2,
                  void *workspace, int64_t workspace_bytes) {
-    using G = Geo4<CB, TG, GW>;
+    using G = Geo4<CB, TG, GW, IH>;
     constexpr int kSmemP = G::kSmemBytes > 8 * 64 * 64 * 4 ? G::kSmemBytes : 8 * 64 * 64 * 4;       // rings, or the 128 KiB of the final exchange
     static pwc::LdsAttrOnce once;
-    if (const int rc = pwc::ensure_lds_attr(once, reinterpret_cast<const void *>(&conv3x3_wino4p_kernel<CB, TG, GW>), kSmemP, "conv3x3_wino4p_kernel"))
+    if (const int rc = pwc::ensure_lds_attr(once, reinterpret_cast<const void *>(&conv3x3_wino4p_kernel<CB, TG, GW, IH>), kSmemP, "conv3x3_wino4p_kernel"))
         return rc;
+    if (IH && (H > IH || W > GW || Cin % kCK || (int64_t)(G::kImg - 1) * bsx * 4 + (int64_t)kCK * H * W * 4 > 0x7fffffffLL))
+        PWC_FAIL(PWC_EUNSUPPORTED, "pwc_conv3x3_wino4_fwd: stacked tile groups need H <= %d, W <= %d, Cin %% 4 == 0 and 31-bit offsets", IH, GW);
     const int CoutP = cout_padded4(Cout);
-    constexpr int kTH = G::kGH * TG;
-    const int tiles_x = (W + GW - 1) / GW, tiles_y = (H + kTH - 1) / kTH;
-    const int64_t nblk = (int64_t)B * tiles_x * tiles_y;
+    constexpr int kTH = G::kTH;
+    // stacked: the tile arithmetic (tail split, XCD order) runs over groups of kImg images, as the plain form runs over images
+    const int Bg = (B + G::kImg - 1) / G::kImg;
+    const int tiles_x = (W + GW - 1) / GW, tiles_y = IH ? 1 : (H + kTH - 1) / kTH;
+    const int64_t nblk = (int64_t)Bg * tiles_x * tiles_y;
     if (nblk * ngroups > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino4_fwd: grid too large");
-    TailPlan tp = wino4_tail_plan(B, nblk, ngroups, (Cin + kCK - 1) / kCK, Cout, kTH * GW, split2);
+    TailPlan tp = wino4_tail_plan(Bg, nblk, ngroups, (Cin + kCK - 1) / kCK, Cout, kTH * GW, split2);
     if (tp.ksplit > 1 && (!workspace || workspace_bytes < tp.ws_bytes || (reinterpret_cast<uintptr_t>(workspace) & 15u))) tp = TailPlan{(int)nblk, 1, 0, 0};
     if (tp.main_tiles > 0)
-        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW>), dim3((unsigned)(tp.main_tiles * ngroups)), dim3(kThreads), kSmemP, st,
-                           x, up, bias, y, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, tp.main_tiles, ngroups, split2,
-                           TailSplit{tp.main_tiles / B, 0, 1, 0, nullptr});
+        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(tp.main_tiles * ngroups)), dim3(kThreads), kSmemP, st,
+                           x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, tp.main_tiles, ngroups, split2,
+                           TailSplit{tp.main_tiles / Bg, 0, 1, 0, nullptr});
     if (tp.ksplit > 1) {
         const int ntail = (int)nblk - tp.main_tiles;
         float *ws = static_cast<float *>(workspace);
-        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW>), dim3((unsigned)(ntail * ngroups * tp.ksplit)), dim3(kThreads), kSmemP, st,
-                           x, up, bias, y, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, ntail, ngroups, 0,
-                           TailSplit{ntail / B, tp.main_tiles / B, tp.ksplit, tp.cps, ws});
+        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(ntail * ngroups * tp.ksplit)), dim3(kThreads), kSmemP, st,
+                           x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, ntail, ngroups, 0,
+                           TailSplit{ntail / Bg, tp.main_tiles / Bg, tp.ksplit, tp.cps, ws});
         const int ncout = min(ngroups * G::kCoutT, Cout - co0);
         const int64_t total = (int64_t)ntail * ncout * kTH * (GW / 4);
         hipLaunchKernelGGL(wino4_tail_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           ws, bias, y, tp.ksplit, ntail / B, tp.main_tiles / B, ntail, tiles_x, kTH, GW, H, W, Cout, co0, ncout, bsy, slope, do_leaky, split2, total);
+                           ws, bias, y, tp.ksplit, ntail / Bg, tp.main_tiles / Bg, ntail, tiles_x, kTH, GW, IH, B, H, W, Cout, co0, ncout, bsy, slope,
+                           do_leaky, split2, total);
     }
-    pwc::note_kernel("conv3x3_wino4p_kernel", CB, TG, GW, tp.ksplit, 1, 0);
+    pwc::note_kernel("conv3x3_wino4p_kernel", CB, TG, GW, tp.ksplit, 1, IH);
     return pwc::check_launch("conv3x3_wino4p_kernel");
 }
 
@@ -704,6 +735,19 @@ inline int wino4_gw(int W) {
 // rows of a map covered by the launch with `th`-row workgroups, as a fraction
 inline double wino4_row_fill(int H, int th) { return (double)H / ((H + th - 1) / th * th); }
 
+// Form of one launch with TG tile groups per workgroup (2: the 64-cout launch, 4: the 32-cout one): the plain form with wino4_gw(W)-column
+// groups, or -- for a map too short to fill the workgroup's th rows -- the stacked form (Geo4, IH > 0) where one is built for this TG:
+// GW = 32, IH = 16 for TG = 4 (14x32: dc_conv4's last 32 couts, two images per workgroup) and GW = 16, IH = 8 for TG = 2 (7x16: dc_conv5
+// on the level-4 lattices, four images).  ih = 0: plain, possibly under-filled (the rule refuses that; the launcher still runs it).
+struct W4Form { int gw, th, ih, kimg; };
+inline W4Form wino4_form(int H, int W, int Cin, int tg) {
+    const int gw = wino4_gw(W), th = (gw == 64 ? 4 : 8) * tg;
+    if (wino4_row_fill(H, th) >= 0.85) return W4Form{gw, th, 0, 1};
+    const int sgw = tg == 4 ? 32 : 16, sih = tg == 4 ? 16 : 8, ih = (H + 3) / 4 * 4;      // both stacked forms have 32-row workgroups
+    if (ih == sih && W <= sgw && Cin % kCK == 0 && (double)W / sgw >= 0.85 && (double)H / ih >= 0.85) return W4Form{sgw, 32, sih, 32 / sih};
+    return W4Form{gw, th, 0, 1};
+}
+
 }  // namespace
 
 // Can this layer run here at all?  Dilation 1 (a dilated layer's lattices are not contiguous in memory: no 16-byte pieces),
@@ -713,13 +757,13 @@ static bool wino4_supported(int W, int dilation) { return dilation == 1 && W % 4
 // Does F(4x4,3x3) beat F(2x2,3x3) (pwc_conv3x3_wino_fwd) for this layer?  Rule measured at batch 16 (profiles/r03_wino4_layers.txt):
 // the tile groups are 8 or 16 rows x 64 columns, so the map must fill them, and the launch must cover the chip several times
 // over (a workgroup costs ~10 us outside its K loop).  Option "conv_wino4" = 0 (pwc_set_option, default from PWC_CONV_WINO4) switches the route off (A/B runs).
+// Maps shorter than a workgroup count as filled when a stacked form serves them (wino4_form: the padded images fill it to H / ceil4(H),
+// and coverage counts groups of images); option "w4_stacked" = 0 (PWC_W4_STACKED) refuses those launches -- the round-4 rule.
 extern "C" int pwc_conv3x3_wino4_preferred(int B, int Cin, int H, int W, int Cout, int dilation) {
     if (B <= 0 || Cin < 32 || H <= 0 || W <= 0 || Cout < 32 || !wino4_supported(W, dilation)) return 0;
     const int knob = pwc::option(pwc::OPT_CONV_WINO4);
     if (!knob) return 0;
     const int n32 = cout_padded4(Cout) / 32;
-    const int gw = wino4_gw(W), gh = gw == 64 ? 4 : 8;                 // a tile group is gh rows x gw columns
-    const int tiles_x = (W + gw - 1) / gw;
     const int nchunks = (Cin + kCK - 1) / kCK;
     // every launch the layer splits into must cover the chip: the 64-cout launch (two tile groups per workgroup) and, for an odd number
     // of 32-cout blocks, the 32-cout one (four groups) -- conv3_2 (96 couts @56x128) fails on the latter (128 workgroups, x0.94).  A launch
@@ -732,15 +776,16 @@ extern "C" int pwc_conv3x3_wino4_preferred(int B, int Cin, int H, int W, int Cou
         const int k = wino4_small_ksplit(nwg, nchunks, device_cus());
         return nwg * k >= pwc::option(pwc::OPT_W4_SMALL_MIN_WGS) && nchunks / k >= 6;
     };
-    if (n32 >= 2) {
-        const int th = 2 * gh;
-        if (wino4_row_fill(H, th) < 0.85 || !covers((int64_t)B * tiles_x * ((H + th - 1) / th), n32 / 2)) return 0;
-    }
-    if (n32 & 1) {
-        const int th = 4 * gh;
-        if (wino4_row_fill(H, th) < 0.85 || !covers((int64_t)B * tiles_x * ((H + th - 1) / th), 1)) return 0;
-    }
-    return (double)W / (tiles_x * gw) >= 0.85;
+    auto launch_ok = [&](int tg, int ngroups) {
+        const W4Form f = wino4_form(H, W, Cin, tg);
+        if (f.ih ? !pwc::option(pwc::OPT_W4_STACKED) : wino4_row_fill(H, f.th) < 0.85) return false;
+        const int tiles_x = (W + f.gw - 1) / f.gw;
+        const int64_t nblk = (int64_t)((B + f.kimg - 1) / f.kimg) * tiles_x * (f.ih ? 1 : (H + f.th - 1) / f.th);
+        return covers(nblk, ngroups) && (double)W / (tiles_x * f.gw) >= 0.85;
+    };
+    if (n32 >= 2 && !launch_ok(2, n32 / 2)) return 0;
+    if ((n32 & 1) && !launch_ok(4, 1)) return 0;
+    return 1;
 }
 
 extern "C" int64_t pwc_conv3x3_wino4_packed_bytes(int Cin, int Cout) {
@@ -779,20 +824,23 @@ extern "C" int pwc_conv3x3_wino4_fwd(const void *x, const void *up, const void *
     if (split2 && ((H & 1) || (W & 7) || (y_bstride & 1)))
         PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino4_fwd: PWC_CONV_SPLIT2 needs even H, W %% 8 == 0 and an even batch stride");
     const int n32 = cout_padded4(Cout) / 32;
-    // 64-cout workgroups (4 cout blocks x 2 tile groups) for as many pairs of 32 as there are, one 32-cout launch (2 x 4) for an odd rest
-    if (wino4_gw(W) == 64) {
-        if (n32 >= 2)
-            if (const int rc = launch_wino4<4, 2, 64>(xf, uf, bf, yf, B, Cin, H, W, Cout, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, n32 / 2, split2, workspace, workspace_bytes))
-                return rc;
-        if (n32 & 1)
-            return launch_wino4<2, 4, 64>(xf, uf, bf, yf, B, Cin, H, W, Cout, x_bstride, y_bstride, leaky_slope, do_leaky, st, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes);
-    } else {
-        if (n32 >= 2)
-            if (const int rc = launch_wino4<4, 2, 32>(xf, uf, bf, yf, B, Cin, H, W, Cout, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, n32 / 2, split2, workspace, workspace_bytes))
-                return rc;
-        if (n32 & 1)
-            return launch_wino4<2, 4, 32>(xf, uf, bf, yf, B, Cin, H, W, Cout, x_bstride, y_bstride, leaky_slope, do_leaky, st, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes);
+    // 64-cout workgroups (4 cout blocks x 2 tile groups) for as many pairs of 32 as there are, one 32-cout launch (2 x 4) for an odd rest;
+    // each in the form wino4_form picks for this map (stacked images where the map is shorter than the workgroup)
+#define PWC_W4_ARGS xf, uf, bf, yf, B, Cin, H, W, Cout, x_bstride, y_bstride, leaky_slope, do_leaky, st
+    if (n32 >= 2) {
+        const W4Form f = wino4_form(H, W, Cin, 2);
+        const int rc = f.ih ? launch_wino4<4, 2, 16, 8>(PWC_W4_ARGS, 0, n32 / 2, split2, workspace, workspace_bytes)
+                     : f.gw == 64 ? launch_wino4<4, 2, 64>(PWC_W4_ARGS, 0, n32 / 2, split2, workspace, workspace_bytes)
+                                  : launch_wino4<4, 2, 32>(PWC_W4_ARGS, 0, n32 / 2, split2, workspace, workspace_bytes);
+        if (rc) return rc;
     }
+    if (n32 & 1) {
+        const W4Form f = wino4_form(H, W, Cin, 4);
+        return f.ih ? launch_wino4<2, 4, 32, 16>(PWC_W4_ARGS, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes)
+             : f.gw == 64 ? launch_wino4<2, 4, 64>(PWC_W4_ARGS, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes)
+                          : launch_wino4<2, 4, 32>(PWC_W4_ARGS, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes);
+    }
+#undef PWC_W4_ARGS
     return PWC_OK;
 }
 
@@ -800,11 +848,15 @@ extern "C" int pwc_conv3x3_wino4_fwd(const void *x, const void *up, const void *
 extern "C" int64_t pwc_conv3x3_wino4_workspace_bytes(int B, int Cin, int H, int W, int Cout) {
     if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || !wino4_supported(W, 1)) return 0;
     const int n32 = cout_padded4(Cout) / 32, nchunks = (Cin + kCK - 1) / kCK;
-    const int gw = wino4_gw(W), gh = gw == 64 ? 4 : 8;
-    const int64_t tiles_x = (W + gw - 1) / gw;
+    auto need_of = [&](int tg, int ngroups) {                   // as launch_wino4 plans it, in the form the launcher picks
+        const W4Form f = wino4_form(H, W, Cin, tg);
+        const int Bg = (B + f.kimg - 1) / f.kimg;
+        const int64_t tiles_x = (W + f.gw - 1) / f.gw;
+        return wino4_tail_plan(Bg, (int64_t)Bg * tiles_x * (f.ih ? 1 : (H + f.th - 1) / f.th), ngroups, nchunks, Cout, f.th * f.gw, 0).ws_bytes;
+    };
     int64_t need = 0;
-    if (n32 >= 2) need = max(need, wino4_tail_plan(B, (int64_t)B * tiles_x * ((H + 2 * gh - 1) / (2 * gh)), n32 / 2, nchunks, Cout, 2 * gh * gw, 0).ws_bytes);
-    if (n32 & 1) need = max(need, wino4_tail_plan(B, (int64_t)B * tiles_x * ((H + 4 * gh - 1) / (4 * gh)), 1, nchunks, Cout, 4 * gh * gw, 0).ws_bytes);
+    if (n32 >= 2) need = max(need, need_of(2, n32 / 2));
+    if (n32 & 1) need = max(need, need_of(4, 1));
     return need;
 }
 

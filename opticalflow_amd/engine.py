@@ -167,6 +167,9 @@ class PwcPlan:
         # images of half the size, with contiguous rows: F(4x4) / F(2x2) at their dilation-1 speed instead of strided lattice
         # addressing (dc_conv2 611 -> ~430 us, dc_conv3 679 -> ~470 us at batch 16).  dc_conv5 (dilation 16) is a dilation-2
         # convolution on the dilation-8 lattices; its 64-channel result is brought back to NCHW by pwc_lattice_unsplit_f32.
+        # One level deeper (ctx_lattice4): dc_conv4 runs all 96 couts on F(4x4) and stores ITS result as lattices too, so dc_conv5 is a
+        # dilation-1 F(4x4) layer on 256B images of h/16 x w/16 (7x16 at 448x1024) -- both on the stacked tile groups of
+        # pwc_conv_wino4.hip (several short images per workgroup), where the rule takes them; option "w4_stacked" = 0 restores the 3-level form.
         wino_on = (os.environ.get("PWC_CONV_WINO", "1") != "0" and os.environ.get("PWC_CONV_WINO4", "1") != "0"
                    and (conv_backend != "hip" or _lib.get_option("conv_wino4") != 0))
         self.ctx_lattice = bool(
@@ -175,12 +178,20 @@ class PwcPlan:
             and ops.conv3x3_wino4_preferred(B, level_in_channels(2, self.nd) + DENSE_TOTAL, h2, w2, CONTEXT[0][0])
             and ops.conv3x3_wino4_preferred(4 * B, CONTEXT[0][0], h2 // 2, w2 // 2, CONTEXT[1][0])
             and ops.conv3x3_wino4_preferred(16 * B, CONTEXT[1][0], h2 // 4, w2 // 4, CONTEXT[2][0]))
+        self.ctx_lattice4 = False
         if self.ctx_lattice:
             self.ctx[0] = torch.empty((4 * B, CONTEXT[0][0], h2 // 2, w2 // 2), **kw)
             self.ctx[1] = torch.empty((16 * B, CONTEXT[1][0], h2 // 4, w2 // 4), **kw)
             self.ctx[2] = torch.empty((64 * B, CONTEXT[2][0], h2 // 8, w2 // 8), **kw)
-            self.ctx[3] = torch.empty((64 * B, CONTEXT[3][0], h2 // 8, w2 // 8), **kw)
-            self.ctx4_lat = torch.empty((64 * B, CONTEXT[4][0], h2 // 8, w2 // 8), **kw)
+            self.ctx_lattice4 = bool(
+                h2 % 16 == 0 and w2 % 64 == 0
+                and tuple(self.p["dc_conv4.0.weight"].shape[:2]) == (CONTEXT[3][0], CONTEXT[2][0])
+                and tuple(self.p["dc_conv5.0.weight"].shape[:2]) == (CONTEXT[4][0], CONTEXT[3][0])
+                and ops.conv3x3_wino4_preferred(64 * B, CONTEXT[2][0], h2 // 8, w2 // 8, CONTEXT[3][0])
+                and ops.conv3x3_wino4_preferred(256 * B, CONTEXT[3][0], h2 // 16, w2 // 16, CONTEXT[4][0]))
+            n4, s4 = (256 * B, 16) if self.ctx_lattice4 else (64 * B, 8)      # images / size divisor of dc_conv4's output and dc_conv5
+            self.ctx[3] = torch.empty((n4, CONTEXT[3][0], h2 // s4, w2 // s4), **kw)
+            self.ctx4_lat = torch.empty((n4, CONTEXT[4][0], h2 // s4, w2 // s4), **kw)
 
         self.packed: Dict[str, torch.Tensor] = {}
         self.wino_packed: Dict[str, torch.Tensor] = {}
@@ -226,12 +237,13 @@ class PwcPlan:
                             geo.append(("dc_conv%d.0" % (i + 1), B, cin, co, 2))
                         cin = co
                     if self.ctx_lattice:                      # dc_conv2 / dc_conv3 run as dilation-1 layers on the lattices
-                        for key in ("dc_conv2.0", "dc_conv3.0"):
+                        for key in ("dc_conv2.0", "dc_conv3.0") + (("dc_conv4.0", "dc_conv5.0") if self.ctx_lattice4 else ()):
                             self.wino4_packed[key] = ops.pack_conv3x3_wino4(self.p[key + ".weight"])
                         # dc_conv4 (128 -> 96 on 64B images of h/8 x w/8, e.g. 14x32): its first 64 couts fill F(4x4)'s 32-column tile
                         # groups, a 32-cout F(4x4) launch (32-row workgroups) would be half empty -> those couts stay on F(2x2)
                         w4 = self.p["dc_conv4.0.weight"]
-                        self.dc4_split = bool(w4.shape[0] == 96 and ops.conv3x3_wino4_preferred(64 * B, w4.shape[1], h2 // 8, w2 // 8, 64))
+                        self.dc4_split = bool(not self.ctx_lattice4 and w4.shape[0] == 96
+                                              and ops.conv3x3_wino4_preferred(64 * B, w4.shape[1], h2 // 8, w2 // 8, 64))
                         if self.dc4_split:
                             self._pack_split96("dc_conv4.0")
                 for key, b_, cin, co, l in geo:
@@ -275,6 +287,8 @@ class PwcPlan:
                 out += [(4 * B, c[0], h // 2, w // 2, c[1], 1), (16 * B, c[1], h // 4, w // 4, c[2], 1),
                         (64 * B, c[2], h // 8, w // 8, c[3], 1), (64 * B, c[2], h // 8, w // 8, 64, 1), (64 * B, c[2], h // 8, w // 8, 32, 1),
                         (64 * B, c[3], h // 8, w // 8, c[4], 2)]
+                if getattr(self, "ctx_lattice4", False):       # dc_conv5 as a dilation-1 layer on the level-4 lattices
+                    out.append((256 * B, c[3], h // 16, w // 16, c[4], 1))
         return out
 
     def _workspace_bytes(self, B: int, trunk2: bool) -> int:
@@ -497,6 +511,13 @@ class PwcPlan:
         w4("dc_conv1", self.arena[2], self.ctx[0], True)          # [B,565,H,W]      -> 4B  x [128,H/2,W/2]   (lattices of dilation 2)
         w4("dc_conv2", self.ctx[0], self.ctx[1], True)            # dilation 2 = 1 on those -> 16B x [128,H/4,W/4]
         w4("dc_conv3", self.ctx[1], self.ctx[2], True)            # dilation 4 = 1          -> 64B x [128,H/8,W/8]
+        if self.ctx_lattice4:
+            w4("dc_conv4", self.ctx[2], self.ctx[3], True)        # dilation 8 = 1          -> 256B x [96,H/16,W/16]
+            w4("dc_conv5", self.ctx[3], self.ctx4_lat, False)     # dilation 16 = 1 on those (stacked tile groups: 7x16 images)
+            ops.lattice_unsplit(self.ctx4_lat, B, 4, out=self.ctx[4])
+            self._conv("dc_conv6", self.ctx[4], self.ctx[5], dilation=1)
+            self._conv("dc_conv7", self.ctx[5], self.flow_out, act=False, residual=self.flow[2])
+            return self.flow_out
         if getattr(self, "dc4_split", False):                     # dilation 8 = 1 on the dilation-8 lattices: 64 couts F(4x4) + 32 couts F(2x2)
             self._conv_split96("dc_conv4.0", self.ctx[2], self.ctx[3])
         else:

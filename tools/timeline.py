@@ -29,9 +29,11 @@ def short(n):
     m = (re.search(r"conv3x3_f16w8_kernel<(\d+), (\d+)", n) or re.search(r"conv3x3_f16w8_kernelILi(\d+)ELi(\d+)E", n))
     if m:
         return "f16w8<MT%s,D%s>" % m.groups()
-    m = re.search(r"conv3x3_wino4p?_kernel<(\d+), (\d+)(?:, (\d+))?>", n) or re.search(r"conv3x3_wino4p?_kernelILi(\d+)ELi(\d+)E(?:Li(\d+)E)?", n)
-    if m:
-        return "wino4<CB%s,TG%s%s>" % (m.group(1), m.group(2), ",GW32" if m.group(3) == "32" else "")
+    m = (re.search(r"conv3x3_wino4p?_kernel<(\d+), (\d+)(?:, (\d+))?(?:, (\d+))?>", n)
+         or re.search(r"conv3x3_wino4p?_kernelILi(\d+)ELi(\d+)E(?:Li(\d+)E)?(?:Li(\d+)E)?", n))
+    if m:      # <cout blocks, tile groups, group width, stacked image height (0: one image per workgroup)>
+        return "wino4<CB%s,TG%s%s%s>" % (m.group(1), m.group(2), ",GW%s" % m.group(3) if m.group(3) not in (None, "64") else "",
+                                        ",IH%s" % m.group(4) if m.group(4) not in (None, "0") else "")
     m = re.search(r"conv3x3_wino(8r?)_kernel<(\d+)>", n) or re.search(r"conv3x3_wino(8r?)_kernelILi(\d+)E", n)
     if m:
         return "wino%s<MT%s>" % m.groups()
