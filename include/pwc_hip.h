@@ -23,6 +23,8 @@
  *                       of the flow-warped image, first-order smoothness)
  *   pwc_proxy_loss_bwd  autograd of the same w.r.t. the flow (train_pseudo's / train_fundamental's loss.backward())
  *   pwc_flow_warp_image_fwd  ProxyLabelLoss.warp  train_pseudo.py:122-157, warp_image train_fundamental.py:80-99
+ *   pwc_epipolar_*      _flow_to_pairs / _ransac_F / build_epipolar_mask_from_flow / epipolar_sampson_loss
+ *                       train_fundamental.py:169-382 (the hard epipolar mask and soft Sampson penalty, :459-483)
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -212,6 +214,52 @@ int pwc_proxy_loss_bwd(const void *flow, const void *img1, const void *img2, con
  * out [B,C,H,W] = img sampled at the point above (flow [B,2,h,w], upsampled when (h,w) != (H,W)).  Same declines as the loss. */
 int pwc_flow_warp_image_fwd(const void *img, const void *flow, void *out, int B, int C, int H, int W, int h, int w,
                             int64_t img_bstride, int64_t flow_bstride, int64_t out_bstride, void *stream);
+
+/* Epipolar hard mask and soft Sampson penalty (ABI v13 additions, csrc/pwc_epipolar.hip), restating train_fundamental.py:169-382
+ * as called at :459-483.  All geometry in fp64; integer or fixed-order fp64 reductions, no float atomics: bit-reproducible.
+ * flow [B,2,H,W] f32 (dense planes, batch stride in elements).
+ * pwc_epipolar_pairs: _flow_to_pairs (:169-194).  pts f64 [B,cap,4] = (x, y, x + fu, y + fv) of the grid points
+ *   mgrid[0:H:stride, 0:W:stride] (row-major, cap = ceil(H/stride) * ceil(W/stride)) whose endpoints are finite and whose image
+ *   mask (u8 or f32 [B,H,W], != 0; NULL = none) is set, packed in order; npts int32 [B] = N_b.
+ * pwc_epipolar_ransac: _ransac_F (:236-258) on those pairs.  idx int32 [iters,8] per sample (batch stride idx_bstride elements,
+ *   0 = one table for all) is numpy's rng.choice(N_b, 8, replace=False) sequence, drawn by the caller; hypothesis i fits row i by
+ *   _eight_point_F (:211-225; the vector of the 8th-largest singular value of the 8 x 9 system, as numpy's thin SVD returns),
+ *   counts[B,iters] int32 = #{d < thresh}; the first strictly largest count wins; F_out f64 [B,9] = the refit on its inliers
+ *   (vector of the min(n,9)-th largest singular value), ok_out int32 [B] = 0 when N_b < 8 or the best count < 8 (F_out = 0 then),
+ *   best_out int32 [B] (may be NULL) = the winning index (-1 when N_b < 8).  workspace: pwc_epipolar_ransac_workspace_bytes.
+ * pwc_epipolar_distance: dist f64 [B,H,W] = Sampson d of every pixel (:285-296; x / (x_2 + 1e-12) included) for F f64 [.,9]
+ *   (F_bstride 9 per sample, 0 = one F).
+ * pwc_epipolar_mask: build_epipolar_mask_from_flow (:261-327) from F f64 [B,9] and ok int32 [B]: thr = min(tau, np.quantile(d_finite,
+ *   keep_ratio)) (linear method, numpy's _lerp), mask = finite & d <= thr, relaxed to min(tau, quantile(min_keep)) when
+ *   mean(mask) < min_keep (each step only when its ratio is in (0,1)); mask_out u8 [B,H,W]; thr_out f64 [B] (NaN where the mask is
+ *   all true: fit failed or no finite d); dist_out (may be NULL) receives d.  workspace: pwc_epipolar_mask_workspace_bytes.
+ * pwc_epipolar_loss_fwd / _bwd: epipolar_sampson_loss (:331-382) with F f64 [.,9] rounded to f32 (F_bstride 9 or 0), ok int32
+ *   (NULL = all; ok_bstride 1 or 0: samples with ok == 0 select nothing), mask u8 / f32 [B,H,W] (> 0.5; NULL = all pixels);
+ *   robust 0 = huber(delta), 1 = l1, 2 = plain mean; out f32 [1] = weight * mean over the selected pixels (0 when none).  The
+ *   backward reads grad_out f32 [1] from device memory and writes grad_flow [B,2,H,W] (dense; 0 off the selection).  Both use
+ *   pwc_epipolar_loss_workspace_bytes.
+ * Null operands / bad shapes / short strides / short workspace: PWC_EINVAL before any launch.  PWC_EUNSUPPORTED (nothing launched)
+ * for misaligned operands (f32 / int32 4-byte, f64 8-byte), 2*H*W >= 2^31, B > 65535, NaN thresholds or delta <= 0. */
+int pwc_epipolar_pairs(const void *flow, const void *mask, int mask_u8, void *pts, void *npts, int B, int H, int W, int stride,
+                       int64_t flow_bstride, int64_t mask_bstride, void *stream);
+int64_t pwc_epipolar_ransac_workspace_bytes(int B, int iters);
+int pwc_epipolar_ransac(const void *pts, const void *npts, int cap, const void *idx, int64_t idx_bstride, int B, int iters,
+                        double thresh, void *F_out, void *ok_out, void *best_out, void *counts, void *workspace,
+                        int64_t workspace_bytes, void *stream);
+int pwc_epipolar_distance(const void *flow, const void *F, int64_t F_bstride, void *dist, int B, int H, int W,
+                          int64_t flow_bstride, void *stream);
+int64_t pwc_epipolar_mask_workspace_bytes(int B, int H, int W);
+int pwc_epipolar_mask(const void *flow, const void *F, const void *ok, void *mask_out, void *thr_out, void *dist_out,
+                      int B, int H, int W, double tau, double keep_ratio, double min_keep, int64_t flow_bstride,
+                      void *workspace, int64_t workspace_bytes, void *stream);
+int64_t pwc_epipolar_loss_workspace_bytes(int B, int H, int W);
+int pwc_epipolar_loss_fwd(const void *flow, const void *F, int64_t F_bstride, const void *ok, int64_t ok_bstride,
+                          const void *mask, int mask_u8, void *out, int B, int H, int W, int robust, double delta, double weight,
+                          int64_t flow_bstride, int64_t mask_bstride, void *workspace, int64_t workspace_bytes, void *stream);
+int pwc_epipolar_loss_bwd(const void *flow, const void *F, int64_t F_bstride, const void *ok, int64_t ok_bstride,
+                          const void *mask, int mask_u8, const void *grad_out, void *grad_flow, int B, int H, int W, int robust,
+                          double delta, double weight, int64_t flow_bstride, int64_t mask_bstride, void *workspace,
+                          int64_t workspace_bytes, void *stream);
 
 /* Backward warp of x by (flow_scale * flo): bilinear, zero padding, times the validity mask
  * [sum of in-bounds bilinear weights >= mask_threshold]  (PWCNet.py:141-177).

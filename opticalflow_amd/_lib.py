@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_char_p, c_float, c_int, c_int64, c_uint, c_void_p
+from ctypes import c_char_p, c_double, c_float, c_int, c_int64, c_uint, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PWC_HIP_LIB: alternative build of the same C ABI (kernel experiments); default = the in-tree library
@@ -53,6 +53,18 @@ SIGNATURES = {
     "pwc_proxy_loss_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_float] * 3 + [c_int64] * 4
                            + [c_void_p, c_int64, c_void_p]),
     "pwc_flow_warp_image_fwd": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_int64] * 3 + [c_void_p]),
+    "pwc_epipolar_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 2 + [c_void_p]),
+    "pwc_epipolar_ransac_workspace_bytes": (c_int64, [c_int, c_int]),
+    "pwc_epipolar_ransac": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_double] + [c_void_p] * 5
+                            + [c_int64, c_void_p]),
+    "pwc_epipolar_distance": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int64, c_void_p]),
+    "pwc_epipolar_mask_workspace_bytes": (c_int64, [c_int] * 3),
+    "pwc_epipolar_mask": (c_int, [c_void_p] * 6 + [c_int] * 3 + [c_double] * 3 + [c_int64, c_void_p, c_int64, c_void_p]),
+    "pwc_epipolar_loss_workspace_bytes": (c_int64, [c_int] * 3),
+    "pwc_epipolar_loss_fwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p] + [c_int] * 4
+                              + [c_double] * 2 + [c_int64] * 2 + [c_void_p, c_int64, c_void_p]),
+    "pwc_epipolar_loss_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int, c_void_p, c_void_p]
+                              + [c_int] * 4 + [c_double] * 2 + [c_int64] * 2 + [c_void_p, c_int64, c_void_p]),
     "pwc_conv3x3_packed_bytes": (c_int64, [c_int, c_int, c_int]),
     "pwc_conv3x3_pack": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "pwc_conv2d_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

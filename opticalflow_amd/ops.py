@@ -783,3 +783,218 @@ class ProxyLossFunction(torch.autograd.Function):
         flow, img1, img2, mask = ctx.saved_tensors
         gf = proxy_loss_backward(flow, img1, img2, mask, grad_out, *ctx.cfg)
         return gf, None, None, None, None, None, None
+
+
+# ---------------------------------------------------------------- epipolar mask + soft Sampson penalty (train_fundamental)
+ROBUST_CODES = {"huber": 0, "l1": 1}   # anything else: the plain mean (code 2), as epipolar_sampson_loss
+
+
+def _flow_arg(flow: torch.Tensor, name: str = "flow_full") -> Tuple[torch.Tensor, int]:
+    if not isinstance(flow, torch.Tensor) or not flow.is_cuda:
+        raise PwcHipError("%s must be a ROCm device tensor: the epipolar path has no CPU fallback" % name)
+    if flow.dim() != 4 or flow.shape[1] != 2 or flow.dtype != torch.float32:
+        raise ValueError("%s must be float32 [B,2,H,W], got %s %s" % (name, flow.dtype, tuple(flow.shape)))
+    flow = densify(flow)
+    return flow, _plane_dense(flow, name)
+
+
+def _nonzero_mask_arg(mask: Optional[torch.Tensor], B: int, H: int, W: int, device) -> Tuple[Optional[torch.Tensor], int]:
+    """Image mask as pwc_epipolar_pairs reads it (value != 0, numpy's astype(bool)): bool / uint8 as bytes, float32 as is."""
+    if mask is None:
+        return None, 0
+    if mask.dim() == 4:
+        mask = mask[:, 0]
+    if tuple(mask.shape) != (B, H, W) or mask.device != device:
+        raise ValueError("img_mask_bhw must be [B,H,W] or [B,1,H,W] = %s on %s, got %s" % ((B, H, W), device, tuple(mask.shape)))
+    if mask.dtype in (torch.bool, torch.uint8):
+        return mask.contiguous().view(torch.uint8), 1
+    if mask.dtype == torch.float32:
+        return mask.contiguous(), 0
+    return (mask != 0).contiguous().view(torch.uint8), 1
+
+
+def epipolar_pairs(flow: torch.Tensor, stride: int = 4, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """_flow_to_pairs of train_fundamental.py:169-194, batched: (pts float64 [B,cap,4] = (x, y, x+fu, y+fv) packed in grid order,
+    N int32 [B] on the device).  Rows past N_b are unwritten."""
+    lib = _lib.load()
+    flow, bsf = _flow_arg(flow)
+    B, _, H, W = flow.shape
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be >= 1")
+    m, u8 = _nonzero_mask_arg(mask, B, H, W, flow.device)
+    cap = -(-H // stride) * -(-W // stride)
+    pts = torch.empty((B, cap, 4), dtype=torch.float64, device=flow.device)
+    n = torch.empty(B, dtype=torch.int32, device=flow.device)
+    with torch.cuda.device(flow.device):
+        rc = lib.pwc_epipolar_pairs(flow.data_ptr(), m.data_ptr() if m is not None else None, u8, pts.data_ptr(), n.data_ptr(),
+                                    B, H, W, stride, bsf, H * W, _stream(flow))
+    check(rc, "pwc_epipolar_pairs")
+    return pts, n
+
+
+def epipolar_ransac(pts: torch.Tensor, n: torch.Tensor, idx: torch.Tensor, thresh: float = 0.5):
+    """_ransac_F of train_fundamental.py:236-258 on epipolar_pairs output, with the caller's index table idx int32 [iters,8]
+    (shared) or [B,iters,8].  Returns (F float64 [B,9], ok int32 [B], best int32 [B], counts int32 [B,iters]); no host sync."""
+    lib = _lib.load()
+    if pts.dim() != 3 or pts.shape[2] != 4 or pts.dtype != torch.float64 or not pts.is_cuda or not pts.is_contiguous():
+        raise ValueError("pts must be a contiguous float64 [B,cap,4] device tensor")
+    B, cap, _ = pts.shape
+    if idx.dtype != torch.int32 or idx.device != pts.device or idx.shape[-1] != 8 or idx.dim() not in (2, 3):
+        raise ValueError("idx must be int32 [iters,8] or [B,iters,8] on %s" % pts.device)
+    idx = idx.contiguous()
+    iters = idx.shape[-2]
+    ibs = 0 if idx.dim() == 2 else 8 * iters
+    if idx.dim() == 3 and idx.shape[0] != B:
+        raise ValueError("idx batch %d != %d" % (idx.shape[0], B))
+    if n.dtype != torch.int32 or tuple(n.shape) != (B,) or n.device != pts.device:
+        raise ValueError("n must be int32 [B] on %s" % pts.device)
+    dev = pts.device
+    F = torch.empty((B, 9), dtype=torch.float64, device=dev)
+    ok = torch.empty(B, dtype=torch.int32, device=dev)
+    best = torch.empty(B, dtype=torch.int32, device=dev)
+    counts = torch.empty((B, iters), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        nb = lib.pwc_epipolar_ransac_workspace_bytes(B, iters)
+        if nb < 0:
+            raise ValueError("bad RANSAC geometry")
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+        rc = lib.pwc_epipolar_ransac(pts.data_ptr(), n.contiguous().data_ptr(), cap, idx.data_ptr(), ibs, B, iters, float(thresh),
+                                     F.data_ptr(), ok.data_ptr(), best.data_ptr(), counts.data_ptr(), ws.data_ptr(), nb,
+                                     torch.cuda.current_stream(dev).cuda_stream)
+    check(rc, "pwc_epipolar_ransac")
+    return F, ok, best, counts
+
+
+def _F_arg(F, B: int, device) -> Tuple[torch.Tensor, int]:
+    """F as float64 [9] (shared, batch stride 0) or [B,9] on the device; accepts numpy / torch [3,3] or torch [B,3,3]."""
+    if not isinstance(F, torch.Tensor):
+        F = torch.as_tensor(F)
+    F = F.to(device=device, dtype=torch.float64)
+    if F.dim() == 2 and tuple(F.shape) == (3, 3):
+        return F.reshape(9).contiguous(), 0
+    if F.dim() == 3 and tuple(F.shape[1:]) == (3, 3) and F.shape[0] in (1, B):
+        return F.reshape(-1, 9).contiguous(), (9 if F.shape[0] == B and B > 1 else 0)
+    if F.dim() == 2 and tuple(F.shape) == (B, 9):
+        return F.contiguous(), 9
+    raise ValueError("F must be [3,3] or [B,3,3], got %s" % (tuple(F.shape),))
+
+
+def epipolar_distance(flow: torch.Tensor, F, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Sampson distance of every pixel, float64 [B,H,W] (train_fundamental.py:285-296, pwc_epipolar_distance)."""
+    lib = _lib.load()
+    flow, bsf = _flow_arg(flow)
+    B, _, H, W = flow.shape
+    Fd, fbs = _F_arg(F, B, flow.device)
+    if out is None:
+        out = torch.empty((B, H, W), dtype=torch.float64, device=flow.device)
+    elif tuple(out.shape) != (B, H, W) or out.dtype != torch.float64 or not out.is_contiguous():
+        raise ValueError("out must be contiguous float64 %s" % ((B, H, W),))
+    with torch.cuda.device(flow.device):
+        rc = lib.pwc_epipolar_distance(flow.data_ptr(), Fd.data_ptr(), fbs, out.data_ptr(), B, H, W, bsf, _stream(flow))
+    check(rc, "pwc_epipolar_distance")
+    return out
+
+
+def epipolar_mask(flow: torch.Tensor, F: torch.Tensor, ok: torch.Tensor, tau: float = 1.0, keep_ratio: float = 0.2,
+                  min_keep: float = 0.05, dist_out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Steps 2-5 of build_epipolar_mask_from_flow (train_fundamental.py:284-327) for F float64 [B,9] and ok int32 [B] from
+    epipolar_ransac: (mask bool [B,1,H,W], thr float64 [B], NaN where the mask is all true).  No host sync."""
+    lib = _lib.load()
+    flow, bsf = _flow_arg(flow)
+    B, _, H, W = flow.shape
+    dev = flow.device
+    F = F.to(device=dev, dtype=torch.float64).reshape(B, 9).contiguous()
+    ok = ok.to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+    mask = torch.empty((B, 1, H, W), dtype=torch.bool, device=dev)
+    thr = torch.empty(B, dtype=torch.float64, device=dev)
+    if dist_out is not None and (tuple(dist_out.shape) != (B, H, W) or dist_out.dtype != torch.float64 or not dist_out.is_contiguous()):
+        raise ValueError("dist_out must be contiguous float64 %s" % ((B, H, W),))
+    with torch.cuda.device(dev):
+        nb = lib.pwc_epipolar_mask_workspace_bytes(B, H, W)
+        if nb < 0:
+            raise ValueError("bad mask geometry")
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+        rc = lib.pwc_epipolar_mask(flow.data_ptr(), F.data_ptr(), ok.data_ptr(), mask.data_ptr(), thr.data_ptr(),
+                                   dist_out.data_ptr() if dist_out is not None else None, B, H, W, float(tau), float(keep_ratio),
+                                   float(min_keep), bsf, ws.data_ptr(), nb, _stream(flow))
+    check(rc, "pwc_epipolar_mask")
+    return mask, thr
+
+
+def _loss_args(flow, F, ok, valid_mask):
+    flow, bsf = _flow_arg(flow)
+    B, _, H, W = flow.shape
+    Fd, fbs = _F_arg(F, B, flow.device)
+    okt, obs = None, 0
+    if ok is not None:
+        okt = torch.as_tensor(ok).to(device=flow.device, dtype=torch.int32).reshape(-1).contiguous()
+        if okt.numel() not in (1, B):
+            raise ValueError("ok must hold 1 or B values")
+        obs = 1 if okt.numel() == B and B > 1 else 0
+    m, u8, bsm = _mask_arg(valid_mask, B, H, W)
+    if m is not None and m.device != flow.device:
+        raise ValueError("valid_mask must be on %s" % flow.device)
+    return flow, bsf, (B, H, W), Fd, fbs, okt, obs, m, u8, bsm
+
+
+def _loss_workspace(B, H, W, device):
+    nb = _lib.load().pwc_epipolar_loss_workspace_bytes(B, H, W)
+    if nb < 0:
+        raise ValueError("bad loss geometry")
+    return torch.empty((nb + 7) // 8, dtype=torch.int64, device=device), nb
+
+
+def epipolar_loss(flow: torch.Tensor, F, ok=None, valid_mask: Optional[torch.Tensor] = None, robust: str = "huber",
+                  delta: float = 1.0, weight: float = 0.1) -> torch.Tensor:
+    """float32 [] = epipolar_sampson_loss (train_fundamental.py:331-382; pwc_epipolar_loss_fwd), 0 when nothing is selected or
+    every fit failed.  No host synchronisation."""
+    lib = _lib.load()
+    flow, bsf, (B, H, W), Fd, fbs, okt, obs, m, u8, bsm = _loss_args(flow, F, ok, valid_mask)
+    out = torch.empty(1, dtype=torch.float32, device=flow.device)
+    with torch.cuda.device(flow.device):
+        ws, nb = _loss_workspace(B, H, W, flow.device)
+        rc = lib.pwc_epipolar_loss_fwd(flow.data_ptr(), Fd.data_ptr(), fbs, okt.data_ptr() if okt is not None else None, obs,
+                                       m.data_ptr() if m is not None else None, u8, out.data_ptr(), B, H, W,
+                                       ROBUST_CODES.get(robust, 2), float(delta), float(weight), bsf, bsm, ws.data_ptr(), nb,
+                                       _stream(flow))
+    check(rc, "pwc_epipolar_loss_fwd")
+    return out[0]
+
+
+def epipolar_loss_backward(flow: torch.Tensor, F, ok, valid_mask: Optional[torch.Tensor], grad_out: torch.Tensor,
+                           robust: str = "huber", delta: float = 1.0, weight: float = 0.1) -> torch.Tensor:
+    """grad_flow [B,2,H,W] of epipolar_loss for the upstream gradient grad_out (a float32 device scalar; no host sync)."""
+    lib = _lib.load()
+    flow, bsf, (B, H, W), Fd, fbs, okt, obs, m, u8, bsm = _loss_args(flow, F, ok, valid_mask)
+    g = grad_out.to(device=flow.device, dtype=torch.float32).contiguous().reshape(1)
+    gf = torch.empty((B, 2, H, W), dtype=torch.float32, device=flow.device)
+    with torch.cuda.device(flow.device):
+        ws, nb = _loss_workspace(B, H, W, flow.device)
+        rc = lib.pwc_epipolar_loss_bwd(flow.data_ptr(), Fd.data_ptr(), fbs, okt.data_ptr() if okt is not None else None, obs,
+                                       m.data_ptr() if m is not None else None, u8, g.data_ptr(), gf.data_ptr(), B, H, W,
+                                       ROBUST_CODES.get(robust, 2), float(delta), float(weight), bsf, bsm, ws.data_ptr(), nb,
+                                       _stream(flow))
+    check(rc, "pwc_epipolar_loss_bwd")
+    return gf
+
+
+class EpipolarSampsonFunction(torch.autograd.Function):
+    """autograd of epipolar_loss w.r.t. the flow (F, ok and the mask are constants): apply(flow, F, ok, valid_mask, robust,
+    delta, weight) -> float32 scalar.  Under torch.autocast the flow is cast to float32."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, flow, F, ok=None, valid_mask=None, robust="huber", delta=1.0, weight=0.1):
+        ctx.save_for_backward(flow)
+        ctx.consts = (F, ok, valid_mask)
+        ctx.cfg = (robust, float(delta), float(weight))
+        return epipolar_loss(flow, F, ok, valid_mask, *ctx.cfg)
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        (flow,) = ctx.saved_tensors
+        F, ok, m = ctx.consts
+        gf = epipolar_loss_backward(flow, F, ok, m, grad_out, *ctx.cfg)
+        return gf, None, None, None, None, None, None
