@@ -186,13 +186,16 @@ def _conv(sd: Dict[str, torch.Tensor], name: str, x: torch.Tensor, stride: int =
           act: bool = True) -> torch.Tensor:
     """conv() helper of PWCNet.py:26-30 (Sequential -> key suffix '.0') or predict_flow :32-33."""
     key = name + ".0" if (name + ".0.weight") in sd else name
-    y = F.conv2d(x, sd[key + ".weight"], sd[key + ".bias"], stride=stride, padding=dilation, dilation=dilation)
+    # float64 sums rounded once to the input's dtype: the float32 forward then does not depend on the host's convolution algorithm
+    y = F.conv2d(x.double(), sd[key + ".weight"].double(), sd[key + ".bias"].double(), stride=stride, padding=dilation,
+                 dilation=dilation).to(x.dtype)
     return leaky_relu(y) if act else y
 
 
 def _deconv(sd, name, x):
     """deconv() helper PWCNet.py:35-36: ConvTranspose2d(k=4, s=2, p=1)."""
-    return F.conv_transpose2d(x, sd[name + ".weight"], sd[name + ".bias"], stride=2, padding=1)
+    return F.conv_transpose2d(x.double(), sd[name + ".weight"].double(), sd[name + ".bias"].double(), stride=2,
+                              padding=1).to(x.dtype)
 
 
 def pwc_forward(sd: Dict[str, torch.Tensor], x: torch.Tensor, normalize_corr: bool = False,

@@ -3,7 +3,8 @@ operator, computed from the launch's own recorded inputs, with a per-element bou
 options that send layers to different kernel routes; then flow2 (and the training-mode tuple up to 256x512) end to end against the
 float64 oracle with a MAX per-pixel endpoint-error bound; then the union of routes reached against a fixed list.
 
-fp16 / fp16-strict plans and multi-GPU runs are outside this audit (their error model is relative to the flow, not per element)."""
+The fp16 / fp16-strict plans have their own per-launch audit (tests/test_gpu_launch_audit_f16.py, tests/launch_audit_f16.py: half
+operands, fp32 accumulation, one rounding to half at the store); multi-GPU runs are outside both."""
 import time
 
 import pytest
