@@ -23,6 +23,9 @@
  *                       of the flow-warped image, first-order smoothness)
  *   pwc_proxy_loss_bwd  autograd of the same w.r.t. the flow (train_pseudo's / train_fundamental's loss.backward())
  *   pwc_flow_warp_image_fwd  ProxyLabelLoss.warp  train_pseudo.py:122-157, warp_image train_fundamental.py:80-99
+ *   pwc_sup_flow_loss_* MaskedCharbonnier on upsample_flow_to(flow2) train.py:31-48 + :69-72, train2.py:114-122, and
+ *                       compute_epe train2.py:100-111 (forward, and backward w.r.t. the low-resolution flow)
+ *   pwc_sup_multiscale_loss_*  supervised_multiscale_loss train2.py:124-167 (all levels in one launch, forward and backward)
  *   pwc_epipolar_*      _flow_to_pairs / _ransac_F / build_epipolar_mask_from_flow / epipolar_sampson_loss
  *                       train_fundamental.py:169-382 (the hard epipolar mask and soft Sampson penalty, :459-483)
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
@@ -214,6 +217,60 @@ int pwc_proxy_loss_bwd(const void *flow, const void *img1, const void *img2, con
  * out [B,C,H,W] = img sampled at the point above (flow [B,2,h,w], upsampled when (h,w) != (H,W)).  Same declines as the loss. */
 int pwc_flow_warp_image_fwd(const void *img, const void *flow, void *out, int B, int C, int H, int W, int h, int w,
                             int64_t img_bstride, int64_t flow_bstride, int64_t out_bstride, void *stream);
+
+/* Supervised flow losses (ABI v13 additions, csrc/pwc_sup_loss.hip), restating train.py / train2.py.  fp32, fixed-order fp64
+ * partial sums, no float atomics: bit-reproducible.  torch's index arithmetic in fp32 (no fused multiply-add):
+ *   bilinear, align_corners=False: scale = (float)in / (float)out;  s = max(scale * ((float)dst + 0.5) - 0.5, 0);  i0 = (int)s;
+ *     i1 = i0 + (i0 < in-1);  l1 = s - i0;  l0 = 1 - l1;   nearest: min((int)floorf((float)dst * scale), in-1).
+ * pwc_sup_flow_loss_fwd: masked Charbonnier / EPE of pred [B,2,h,w] upsampled to gt [B,2,H,W] (train.py:31-48 + :69-72 with
+ *   upsample_flow_to of data_processing_or.py:300-310, train2.py:114-122, compute_epe train2.py:100-111 on :202-213):
+ *   up = interpolate(pred, (H,W), bilinear, align_corners=False) * (float)(W/w, H/h)  (2 <= h <= H, 2 <= w <= W; (h,w) == (H,W)
+ *   is the plain loss), epe = sqrt(|up - gt|^2 + (float)(eps^2));  mask [B,H,W] (a [B,1,H,W] mask is the same plane) f32
+ *   (mask_u8 = 0) or u8 (mask_u8 = 1), or NULL (every pixel, weight 1).  mask_rule 0: loss = sum(epe [m > 0.5]) / max(sum [m > 0.5], 1)
+ *   (MaskedCharbonnier); mask_rule 1: loss = sum(epe m) / (sum m + 1e-8) (compute_epe; eps 0); no mask: the mean.  Writes float
+ *   out[2] = {loss, den} in device memory; the upsampled flow is sampled on the fly, never written.
+ * pwc_sup_flow_loss_bwd: grad_pred [B,2,h,w] (dense) = grad_out[0] d loss / d pred, reading grad_out[0] and den = fwd_out[1] (the
+ *   forward's out) from device memory (no host sync); den gets no gradient.  A row pass sums along X into [B,2,H,w] fp64 in the
+ *   workspace, a column pass along Y: each low-resolution pixel gathers the full-resolution pixels whose taps use it, in order.
+ * pwc_sup_flow_loss_workspace_bytes: the forward's (backward = 0: 16 bytes per 1024 pixels) or the backward's (backward = 1; also
+ *   >= the forward's).
+ * pwc_sup_multiscale_loss_fwd: supervised_multiscale_loss (train2.py:124-167) over L <= 8 levels, one launch for all of them.
+ *   Host arrays: preds[L] device pointers to [B,2,h_l,w_l] f32 (batch strides pred_bstrides[L]; NULL = dense), level_hw[2L] =
+ *   (h_l, w_l), weights[L].  gt [B,2,H,W] f32, mask [B,H,W] f32 / u8 or NULL (weight 1), images [B,6,H,W] f32 = (im1, im2) (read
+ *   only when a lambda is > 0; may be NULL otherwise).  Per level: gt_s = bilinear downsample of gt * (1 / (float)(W/w), 1 /
+ *   (float)(H/h)), mask_s = nearest mask (raw), charb = sum(sqrt(|pred - gt_s|^2 + eps^2) [mask_s > 0.5]) / max(sum [.], 1);
+ *   lambda_photo > 0: photo = sum_c |im1_s - grid_sample(im2_s, (x + u, y + v), bilinear, zeros, align_corners=True)| mask_s /
+ *   (sum mask_s + 1e-8) (:44-77); lambda_smooth > 0: smooth = mean(|dx pred| exp(-mean_c |dx im1_s|)) + the same along y (:80-97);
+ *   im1_s / im2_s are bilinear (align_corners=False) downsamples, written to the workspace by a resize launch.
+ *   out float [1 + 3L] in device memory = {total = sum_l w_l lvl_l, lvl_l = charb + lambda_photo photo + lambda_smooth smooth,
+ *   den_c[L] = max(sum [mask_s > 0.5], 1), den_p[L] = sum mask_s + 1e-8}.
+ * pwc_sup_multiscale_loss_bwd: grads[L] (host array of device pointers, dense [B,2,h_l,w_l]) = grad_out[0] d total / d pred_l,
+ *   elementwise, reading grad_out[0] and the forward's out (fwd_out, for den_c / den_p) from device memory; photometric slopes of the
+ *   zero-padded im2_s with grid_sample's floor-based taps, sign(0) = 0.  Same arguments and workspace as the forward.
+ * pwc_sup_multiscale_loss_workspace_bytes: partial sums (48 bytes per 1024 pixels) + with_images: im1_s / im2_s of every level.
+ * Null operands / bad shapes / short strides / short workspace / negative eps or lambda: PWC_EINVAL before any launch.
+ * PWC_EUNSUPPORTED (nothing launched) when h or w < 2, h > H, w > W, L > 8, an f32 operand is not 4-byte aligned, 6*H*W >= 2^31
+ * (2*H*W for the flow loss) or B > 65535. */
+int64_t pwc_sup_flow_loss_workspace_bytes(int B, int H, int W, int h, int w, int backward);
+int pwc_sup_flow_loss_fwd(const void *pred, const void *gt, const void *mask, int mask_u8, int mask_rule, void *out,
+                          int B, int H, int W, int h, int w, double eps, int64_t pred_bstride, int64_t gt_bstride,
+                          int64_t mask_bstride, void *workspace, int64_t workspace_bytes, void *stream);
+int pwc_sup_flow_loss_bwd(const void *pred, const void *gt, const void *mask, int mask_u8, int mask_rule,
+                          const void *fwd_out, const void *grad_out, void *grad_pred, int B, int H, int W, int h, int w,
+                          double eps, int64_t pred_bstride, int64_t gt_bstride, int64_t mask_bstride, void *workspace,
+                          int64_t workspace_bytes, void *stream);
+int64_t pwc_sup_multiscale_loss_workspace_bytes(int B, int H, int W, int L, const int *level_hw, int with_images);
+int pwc_sup_multiscale_loss_fwd(const void *const *preds, const int64_t *pred_bstrides, const int *level_hw,
+                                const float *weights, int L, const void *gt, const void *mask, int mask_u8,
+                                const void *images, void *out, int B, int H, int W, double eps, float lambda_photo,
+                                float lambda_smooth, int64_t gt_bstride, int64_t mask_bstride, int64_t img_bstride,
+                                void *workspace, int64_t workspace_bytes, void *stream);
+int pwc_sup_multiscale_loss_bwd(const void *const *preds, const int64_t *pred_bstrides, const int *level_hw,
+                                const float *weights, int L, const void *gt, const void *mask, int mask_u8,
+                                const void *images, const void *fwd_out, const void *grad_out, void *const *grads,
+                                int B, int H, int W, double eps, float lambda_photo, float lambda_smooth,
+                                int64_t gt_bstride, int64_t mask_bstride, int64_t img_bstride, void *workspace,
+                                int64_t workspace_bytes, void *stream);
 
 /* Epipolar hard mask and soft Sampson penalty (ABI v13 additions, csrc/pwc_epipolar.hip), restating train_fundamental.py:169-382
  * as called at :459-483.  All geometry in fp64; integer or fixed-order fp64 reductions, no float atomics: bit-reproducible.

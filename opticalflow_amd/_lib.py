@@ -53,6 +53,16 @@ SIGNATURES = {
     "pwc_proxy_loss_bwd": (c_int, [c_void_p] * 4 + [c_int, c_void_p, c_void_p] + [c_int] * 6 + [c_float] * 3 + [c_int64] * 4
                            + [c_void_p, c_int64, c_void_p]),
     "pwc_flow_warp_image_fwd": (c_int, [c_void_p] * 3 + [c_int] * 6 + [c_int64] * 3 + [c_void_p]),
+    "pwc_sup_flow_loss_workspace_bytes": (c_int64, [c_int] * 6),
+    "pwc_sup_flow_loss_fwd": (c_int, [c_void_p] * 3 + [c_int, c_int, c_void_p] + [c_int] * 5 + [c_double] + [c_int64] * 3
+                              + [c_void_p, c_int64, c_void_p]),
+    "pwc_sup_flow_loss_bwd": (c_int, [c_void_p] * 3 + [c_int, c_int] + [c_void_p] * 3 + [c_int] * 5 + [c_double] + [c_int64] * 3
+                              + [c_void_p, c_int64, c_void_p]),
+    "pwc_sup_multiscale_loss_workspace_bytes": (c_int64, [c_int] * 4 + [c_void_p, c_int]),
+    "pwc_sup_multiscale_loss_fwd": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 2 + [c_int] * 3
+                                    + [c_double, c_float, c_float] + [c_int64] * 3 + [c_void_p, c_int64, c_void_p]),
+    "pwc_sup_multiscale_loss_bwd": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [c_int] * 3
+                                    + [c_double, c_float, c_float] + [c_int64] * 3 + [c_void_p, c_int64, c_void_p]),
     "pwc_epipolar_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 2 + [c_void_p]),
     "pwc_epipolar_ransac_workspace_bytes": (c_int64, [c_int, c_int]),
     "pwc_epipolar_ransac": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_double] + [c_void_p] * 5

@@ -8,6 +8,7 @@ does no validation and silently assumes contiguous NCHW
 """
 from __future__ import annotations
 
+import ctypes
 import math
 import os
 from typing import Optional, Tuple
@@ -783,6 +784,266 @@ class ProxyLossFunction(torch.autograd.Function):
         flow, img1, img2, mask = ctx.saved_tensors
         gf = proxy_loss_backward(flow, img1, img2, mask, grad_out, *ctx.cfg)
         return gf, None, None, None, None, None, None
+
+
+# ---------------------------------------------------------------- supervised flow losses (train.py / train2.py)
+SUP_MAX_LEVELS = 8
+MASK_RULES = {"threshold": 0, "raw": 1}   # MaskedCharbonnier's [m > 0.5] / max(sum, 1); compute_epe's raw m / (sum + 1e-8)
+
+
+def _sup_geometry_ok(H: int, W: int, h: int, w: int) -> bool:
+    return 2 <= h <= H and 2 <= w <= W
+
+
+def sup_flow_loss_supported(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor] = None) -> bool:
+    """Python mirror of the rules under which pwc_sup_flow_loss_fwd / _bwd launch (include/pwc_hip.h): ROCm device tensors,
+    pred [B,2,h,w] and gt [B,2,H,W] with 2 <= h <= H, 2 <= w <= W, 2*H*W < 2^31, B <= 65535; mask [B,H,W] or [B,1,H,W]."""
+    if not (isinstance(pred, torch.Tensor) and isinstance(gt, torch.Tensor) and pred.is_cuda and gt.is_cuda):
+        return False
+    if pred.dim() != 4 or gt.dim() != 4 or pred.shape[1] != 2 or gt.shape[1] != 2 or pred.shape[0] != gt.shape[0]:
+        return False
+    B, _, H, W = gt.shape
+    if mask is not None and (not mask.is_cuda or tuple(mask.shape) not in ((B, H, W), (B, 1, H, W))):
+        return False
+    return _sup_geometry_ok(H, W, pred.shape[2], pred.shape[3]) and 2 * H * W < 2 ** 31 and 1 <= B <= 65535
+
+
+def sup_multiscale_loss_supported(preds, gt: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                                  images: Optional[torch.Tensor] = None) -> bool:
+    """Mirror of pwc_sup_multiscale_loss_fwd / _bwd's rules: 1..8 levels [B,2,h,w] with 2 <= h <= H, 2 <= w <= W, gt [B,2,H,W],
+    mask [B,H,W] / [B,1,H,W], images [B,6,H,W] (when given), all on the ROCm device, 6*H*W < 2^31, B <= 65535."""
+    if not (isinstance(gt, torch.Tensor) and gt.is_cuda and gt.dim() == 4 and gt.shape[1] == 2):
+        return False
+    B, _, H, W = gt.shape
+    if not (1 <= len(preds) <= SUP_MAX_LEVELS):
+        return False
+    for p in preds:
+        if not (isinstance(p, torch.Tensor) and p.is_cuda and p.dim() == 4 and p.shape[0] == B and p.shape[1] == 2
+                and _sup_geometry_ok(H, W, p.shape[2], p.shape[3])):
+            return False
+    if mask is not None and (not mask.is_cuda or tuple(mask.shape) not in ((B, H, W), (B, 1, H, W))):
+        return False
+    if images is not None and (not images.is_cuda or tuple(images.shape) != (B, 6, H, W)):
+        return False
+    return 6 * H * W < 2 ** 31 and 1 <= B <= 65535
+
+
+def _sup_mask(mask: Optional[torch.Tensor], B: int, H: int, W: int) -> Tuple[Optional[torch.Tensor], int, int]:
+    """[B,H,W] / [B,1,H,W] mask as the kernels read it, raw values kept: (tensor, mask_u8, batch stride).  bool / uint8 -> bytes,
+    float32 as is, any other dtype -> float32."""
+    if mask is None:
+        return None, 0, 0
+    if mask.dim() == 4:
+        mask = mask[:, 0]
+    if tuple(mask.shape) != (B, H, W):
+        raise ValueError("mask must be [B,H,W] or [B,1,H,W] = %s, got %s" % ((B, H, W), tuple(mask.shape)))
+    if mask.dtype == torch.bool:
+        m, u8 = mask.contiguous().view(torch.uint8), 1
+    elif mask.dtype == torch.uint8:
+        m, u8 = mask.contiguous(), 1
+    else:
+        m, u8 = mask.contiguous().float(), 0
+    return m, u8, H * W
+
+
+def _f32_dense(t: torch.Tensor, name: str, shape, device) -> Tuple[torch.Tensor, int]:
+    t = densify(t)
+    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != device:
+        raise ValueError("%s must be float32 %s on %s, got %s %s on %s" % (name, tuple(shape), device, t.dtype, tuple(t.shape), t.device))
+    return t, _plane_dense(t, name)
+
+
+def sup_flow_loss_workspace_bytes(B: int, H: int, W: int, h: int, w: int, backward: bool = False) -> int:
+    n = _lib.load().pwc_sup_flow_loss_workspace_bytes(B, H, W, h, w, 1 if backward else 0)
+    if n < 0:
+        raise ValueError("bad flow-loss geometry")
+    return int(n)
+
+
+def _sup_flow_args(pred, gt, mask):
+    if not (isinstance(gt, torch.Tensor) and gt.is_cuda):
+        raise PwcHipError("gt must be a ROCm device tensor: the supervised loss has no CPU fallback")
+    if gt.dim() != 4 or gt.shape[1] != 2:
+        raise ValueError("gt must be [B,2,H,W], got %s" % (tuple(gt.shape),))
+    B, _, H, W = gt.shape
+    if pred.dim() != 4:
+        raise ValueError("pred must be [B,2,h,w], got %s" % (tuple(pred.shape),))
+    h, w = pred.shape[-2:]
+    gt, bsg = _f32_dense(gt, "gt", (B, 2, H, W), gt.device)
+    pred, bsp = _f32_dense(pred, "pred", (B, 2, h, w), gt.device)
+    m, u8, bsm = _sup_mask(mask, B, H, W)
+    if m is not None and m.device != gt.device:
+        raise ValueError("mask must be on %s" % gt.device)
+    return pred, gt, m, u8, (B, H, W, h, w), (bsp, bsg, bsm)
+
+
+def sup_flow_loss(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor] = None, eps: float = 1e-3,
+                  rule: str = "threshold") -> torch.Tensor:
+    """float32 [2] = (loss, den) of the masked Charbonnier (rule "threshold": train.py:31-48 / train2.py:114-122) or the EPE
+    (rule "raw", eps 0: compute_epe train2.py:100-111) of pred [B,2,h,w] upsampled to gt [B,2,H,W] (bilinear, align_corners=False,
+    vectors scaled by W/w, H/h; pred itself when h,w = H,W).  pwc_sup_flow_loss_fwd: no upsampled flow in memory, no host sync."""
+    lib = _lib.load()
+    pred, gt, m, u8, dims, bs = _sup_flow_args(pred, gt, mask)
+    out = torch.empty(2, dtype=torch.float32, device=gt.device)
+    with torch.cuda.device(gt.device):
+        nb = sup_flow_loss_workspace_bytes(*dims)
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
+        rc = lib.pwc_sup_flow_loss_fwd(pred.data_ptr(), gt.data_ptr(), m.data_ptr() if m is not None else None, u8,
+                                       MASK_RULES[rule], out.data_ptr(), *dims, float(eps), *bs, ws.data_ptr(), nb, _stream(gt))
+    check(rc, "pwc_sup_flow_loss_fwd")
+    return out
+
+
+def sup_flow_loss_backward(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Tensor], fwd_out: torch.Tensor,
+                           grad_out: torch.Tensor, eps: float = 1e-3, rule: str = "threshold") -> torch.Tensor:
+    """grad_pred [B,2,h,w] = grad_out[0] d loss / d pred (pwc_sup_flow_loss_bwd; fwd_out = sup_flow_loss's result, read on the
+    device for the denominator; deterministic, no host synchronisation)."""
+    lib = _lib.load()
+    pred, gt, m, u8, dims, bs = _sup_flow_args(pred, gt, mask)
+    fo = fwd_out.to(device=gt.device, dtype=torch.float32).contiguous().reshape(2)
+    g = grad_out.to(device=gt.device, dtype=torch.float32).contiguous().reshape(-1)
+    B, H, W, h, w = dims
+    gp = torch.empty((B, 2, h, w), dtype=torch.float32, device=gt.device)
+    with torch.cuda.device(gt.device):
+        nb = sup_flow_loss_workspace_bytes(*dims, backward=True)
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
+        rc = lib.pwc_sup_flow_loss_bwd(pred.data_ptr(), gt.data_ptr(), m.data_ptr() if m is not None else None, u8,
+                                       MASK_RULES[rule], fo.data_ptr(), g.data_ptr(), gp.data_ptr(), *dims, float(eps), *bs,
+                                       ws.data_ptr(), nb, _stream(gt))
+    check(rc, "pwc_sup_flow_loss_bwd")
+    return gp
+
+
+class FlowLossFunction(torch.autograd.Function):
+    """autograd of the upsampled masked Charbonnier w.r.t. pred: forward pwc_sup_flow_loss_fwd, backward pwc_sup_flow_loss_bwd.
+    Returns float32 [2] = (loss, den); den gets no gradient.  Under torch.autocast the inputs are cast to float32.
+    apply(pred, gt, mask, eps, rule); gt and mask get no gradient (callers route a GT that requires grad to the torch chain)."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, pred, gt, mask=None, eps=1e-3, rule="threshold"):
+        out = sup_flow_loss(pred, gt, mask, eps, rule)
+        ctx.save_for_backward(pred, gt, mask, out)
+        ctx.cfg = (float(eps), rule)
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        pred, gt, mask, out = ctx.saved_tensors
+        return sup_flow_loss_backward(pred, gt, mask, out, grad_out, *ctx.cfg), None, None, None, None
+
+
+def _levels_host(preds, weights):
+    L = len(preds)
+    ptrs = (ctypes.c_void_p * L)(*[p.data_ptr() for p in preds])
+    bss = (ctypes.c_int64 * L)(*[_plane_dense(p, "flow level %d" % i) for i, p in enumerate(preds)])
+    hw = (ctypes.c_int * (2 * L))(*[int(s) for p in preds for s in p.shape[-2:]])
+    wts = (ctypes.c_float * L)(*[float(x) for x in weights])
+    return ptrs, bss, hw, wts
+
+
+def sup_multiscale_loss_workspace_bytes(B: int, H: int, W: int, sizes, with_images: bool) -> int:
+    L = len(sizes)
+    hw = (ctypes.c_int * (2 * L))(*[int(s) for hw_ in sizes for s in hw_])
+    n = _lib.load().pwc_sup_multiscale_loss_workspace_bytes(B, H, W, L, ctypes.cast(hw, ctypes.c_void_p), 1 if with_images else 0)
+    if n < 0:
+        raise ValueError("bad multiscale-loss geometry")
+    return int(n)
+
+
+def _ms_args(preds, gt, mask, images, weights, lambda_photo, lambda_smooth):
+    if not (isinstance(gt, torch.Tensor) and gt.is_cuda):
+        raise PwcHipError("flows_gt must be a ROCm device tensor: the supervised loss has no CPU fallback")
+    if gt.dim() != 4 or gt.shape[1] != 2:
+        raise ValueError("flows_gt must be [B,2,H,W], got %s" % (tuple(gt.shape),))
+    B, _, H, W = gt.shape
+    gt, bsg = _f32_dense(gt, "flows_gt", (B, 2, H, W), gt.device)
+    if not 1 <= len(preds) <= SUP_MAX_LEVELS or len(weights) != len(preds):
+        raise ValueError("1..%d flow levels with one weight each, got %d levels / %d weights" % (SUP_MAX_LEVELS, len(preds), len(weights)))
+    preds = [_f32_dense(p, "flow level %d" % i, (B, 2) + tuple(p.shape[-2:]), gt.device)[0] for i, p in enumerate(preds)]
+    m, u8, bsm = _sup_mask(mask, B, H, W)
+    if m is not None and m.device != gt.device:
+        raise ValueError("masks must be on %s" % gt.device)
+    with_images = lambda_photo > 0.0 or lambda_smooth > 0.0
+    img, bsi = None, 0
+    if with_images:
+        if images is None:
+            raise ValueError("images [B,6,H,W] are needed when lambda_photo or lambda_smooth > 0")
+        img, bsi = _f32_dense(images, "images", (B, 6, H, W), gt.device)
+    return preds, gt, m, u8, img, (bsg, bsm, bsi), (B, H, W), with_images
+
+
+def sup_multiscale_loss(preds, gt: torch.Tensor, mask: Optional[torch.Tensor], images: Optional[torch.Tensor], weights,
+                        lambda_photo: float = 0.0, lambda_smooth: float = 0.0, eps: float = 1e-3) -> torch.Tensor:
+    """float32 [1 + 3L] = (total, level losses [L], Charbonnier denominators [L], photometric denominators [L]) of
+    supervised_multiscale_loss (train2.py:124-167) over the flow levels preds (pwc_sup_multiscale_loss_fwd: one launch for every
+    level, plus a resize launch when a lambda is > 0).  No host synchronisation."""
+    lib = _lib.load()
+    preds, gt, m, u8, img, bs, dims, wi = _ms_args(preds, gt, mask, images, weights, lambda_photo, lambda_smooth)
+    L = len(preds)
+    ptrs, bss, hw, wts = _levels_host(preds, weights)
+    out = torch.empty(1 + 3 * L, dtype=torch.float32, device=gt.device)
+    with torch.cuda.device(gt.device):
+        nb = sup_multiscale_loss_workspace_bytes(*dims, [p.shape[-2:] for p in preds], wi)
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
+        rc = lib.pwc_sup_multiscale_loss_fwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(bss, ctypes.c_void_p),
+                                             ctypes.cast(hw, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p), L, gt.data_ptr(),
+                                             m.data_ptr() if m is not None else None, u8,
+                                             img.data_ptr() if img is not None else None, out.data_ptr(), *dims, float(eps),
+                                             float(lambda_photo), float(lambda_smooth), *bs, ws.data_ptr(), nb, _stream(gt))
+    check(rc, "pwc_sup_multiscale_loss_fwd")
+    return out
+
+
+def sup_multiscale_loss_backward(preds, gt: torch.Tensor, mask: Optional[torch.Tensor], images: Optional[torch.Tensor], weights,
+                                 fwd_out: torch.Tensor, grad_out: torch.Tensor, lambda_photo: float = 0.0,
+                                 lambda_smooth: float = 0.0, eps: float = 1e-3):
+    """Gradients of the total w.r.t. every level (list of dense [B,2,h,w]) for grad_out[0] (pwc_sup_multiscale_loss_bwd; reads
+    the forward's denominators from fwd_out on the device; elementwise, deterministic)."""
+    lib = _lib.load()
+    preds, gt, m, u8, img, bs, dims, wi = _ms_args(preds, gt, mask, images, weights, lambda_photo, lambda_smooth)
+    L = len(preds)
+    ptrs, bss, hw, wts = _levels_host(preds, weights)
+    fo = fwd_out.to(device=gt.device, dtype=torch.float32).contiguous().reshape(1 + 3 * L)
+    g = grad_out.to(device=gt.device, dtype=torch.float32).contiguous().reshape(-1)
+    grads = [torch.empty(tuple(p.shape), dtype=torch.float32, device=gt.device) for p in preds]
+    gptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in grads])
+    with torch.cuda.device(gt.device):
+        nb = sup_multiscale_loss_workspace_bytes(*dims, [p.shape[-2:] for p in preds], wi)
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
+        rc = lib.pwc_sup_multiscale_loss_bwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(bss, ctypes.c_void_p),
+                                             ctypes.cast(hw, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p), L, gt.data_ptr(),
+                                             m.data_ptr() if m is not None else None, u8,
+                                             img.data_ptr() if img is not None else None, fo.data_ptr(), g.data_ptr(),
+                                             ctypes.cast(gptrs, ctypes.c_void_p), *dims, float(eps), float(lambda_photo),
+                                             float(lambda_smooth), *bs, ws.data_ptr(), nb, _stream(gt))
+    check(rc, "pwc_sup_multiscale_loss_bwd")
+    return grads
+
+
+class MultiscaleLossFunction(torch.autograd.Function):
+    """autograd of supervised_multiscale_loss w.r.t. every flow level: forward pwc_sup_multiscale_loss_fwd, backward
+    pwc_sup_multiscale_loss_bwd.  apply(gt, mask, images, weights, lambda_photo, lambda_smooth, *preds) -> float32 [1 + 3L]
+    (total first; only the total carries a gradient).  Under torch.autocast the inputs are cast to float32; gt, mask and images
+    get no gradient."""
+
+    @staticmethod
+    @torch.amp.custom_fwd(device_type="cuda", cast_inputs=torch.float32)
+    def forward(ctx, gt, mask, images, weights, lambda_photo, lambda_smooth, *preds):
+        cfg = (tuple(float(x) for x in weights), float(lambda_photo), float(lambda_smooth))
+        out = sup_multiscale_loss(list(preds), gt, mask, images, cfg[0], cfg[1], cfg[2])
+        ctx.save_for_backward(gt, mask, images, out, *preds)
+        ctx.cfg = cfg
+        return out
+
+    @staticmethod
+    @torch.amp.custom_bwd(device_type="cuda")
+    def backward(ctx, grad_out):
+        gt, mask, images, out, *preds = ctx.saved_tensors
+        w, lp, ls = ctx.cfg
+        grads = sup_multiscale_loss_backward(preds, gt, mask, images, w, out, grad_out, lp, ls)
+        return (None,) * 6 + tuple(grads)
 
 
 # ---------------------------------------------------------------- epipolar mask + soft Sampson penalty (train_fundamental)
