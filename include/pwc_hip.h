@@ -103,7 +103,10 @@ const char *pwc_last_error(void);
  *   last convolution writes the first image's straight into their arena slot; 0: dense pyramid buffers and one copy per level),
  *   "w4_stacked" [PWC_W4_STACKED] 1 (pwc_conv3x3_wino4_preferred takes maps shorter than an F(4x4) workgroup where a stacked form -- several
  *   images per workgroup, each with its own border -- serves them: 14x32 for a 32-cout launch, 7x16 for a 64-cout one; the fp32 plan then
- *   runs dc_conv4 / dc_conv5 on the level-4 lattices; 0: refused, the round-4 context path).
+ *   runs dc_conv4 / dc_conv5 on the level-4 lattices; 0: refused, the round-4 context path),
+ *   "pyr1_wino" [PWC_PYR1_WINO] 1 (fp32 plans: the 16 -> 16 layers conv1aa / conv1b on pwc_pyr1_wino_fwd; 2: both as one
+ *   pwc_pyr1_wino_pair_fwd launch -- measured slower, for A/B runs; 0: pwc_conv2d_fwd) and "pyr1_wino_min_tiles"
+ *   [PWC_PYR1_WINO_MIN_TILES] 512 (8 x 64 tiles a launch needs for it: see pwc_pyr1_wino_preferred).
  * Unknown name: PWC_EINVAL.  A captured HIP graph keeps the kernels chosen at capture time. */
 int pwc_set_option(const char *name, int value);
 int pwc_get_option(const char *name, int *value);
@@ -461,6 +464,25 @@ int pwc_image_conv_s2_c8_f16(const void *x, const void *w, const void *bias, voi
 int64_t pwc_pyramid1_f16_packed_bytes(void);
 int pwc_pyramid1_fused_f16(const void *x, const void *wpack, const void *bias, void *y, int B, int H, int W,
                            float leaky_slope, int64_t x_bstride, int64_t y_bstride, void *stream);
+
+/* The 16 -> 16 layers of the fp32 first pyramid level (conv1aa, conv1b: Conv2d(16,16,3,pad 1) + LeakyReLU, PWCNet.py:53-54) by
+ * Winograd F(2x2,3x3) on the fp32 matrix cores (csrc/pwc_pyr1_wino.hip): 16 multiplications per 2x2 outputs, the whole transformed
+ * filter bank in LDS, no workspace.  x, y: float32 [B,16,H,W] with free batch strides (elements, multiples of 4), 16-byte aligned,
+ * W % 4 == 0 (PWC_EUNSUPPORTED otherwise: such a layer stays on pwc_conv2d_fwd).  up = pwc_pyr1_wino_pack(w): G g Gt of w:[16,16,3,3]
+ * in the order [16 positions][cin % 4][cout][cin / 4], pwc_pyr1_wino_packed_bytes() bytes.  The result differs from pwc_conv2d_fwd
+ * by fp32 rounding only.
+ * pwc_pyr1_wino_pair_fwd: two such layers (x -> up1, bias1 -> up2, bias2 -> y) in one launch; the map between them lives in LDS per
+ * 14 x 60 output tile (its ring outside the image is zero: the second layer pads the first one's output).  x != y.
+ * pwc_pyr1_wino_preferred: 0 = keep pwc_conv2d_fwd (option "pyr1_wino" = 0, W % 4 != 0, or fewer than "pyr1_wino_min_tiles" 8 x 64
+ * tiles in the launch), 1 = layer by layer (the default), 2 = the pair in one launch (option "pyr1_wino" = 2; measured slower at
+ * batch 16, kept for A/B runs). */
+int64_t pwc_pyr1_wino_packed_bytes(void);
+int pwc_pyr1_wino_preferred(int B, int H, int W);
+int pwc_pyr1_wino_pack(const void *w, void *up, void *stream);
+int pwc_pyr1_wino_fwd(const void *x, const void *up, const void *bias, void *y, int B, int H, int W, float leaky_slope,
+                      int64_t x_bstride, int64_t y_bstride, void *stream);
+int pwc_pyr1_wino_pair_fwd(const void *x, const void *up1, const void *bias1, const void *up2, const void *bias2, void *y,
+                           int B, int H, int W, float leaky_slope, int64_t x_bstride, int64_t y_bstride, void *stream);
 
 /* PWC-Net's cost volume (pad 4, kernel 1, max displacement 4, strides 1) on c8 f16 tensors, fp32 accumulation:
  * in1,in2: [B][ceil(C/8)][H][W][8]; out: [B][11][H][W][8] = 81 displacement channels ((dy+4)*9+(dx+4)) + 7 zeros.

@@ -110,6 +110,11 @@ SIGNATURES = {
     "pwc_pyramid1_f16_packed_bytes": (c_int64, []),
     "pwc_pyramid1_fused_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float,
                                        c_int64, c_int64, c_void_p]),
+    "pwc_pyr1_wino_packed_bytes": (c_int64, []),
+    "pwc_pyr1_wino_preferred": (c_int, [c_int, c_int, c_int]),
+    "pwc_pyr1_wino_pack": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "pwc_pyr1_wino_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int64, c_int64, c_void_p]),
+    "pwc_pyr1_wino_pair_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_float, c_int64, c_int64, c_void_p]),
     "pwc_corr81_c8_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_uint, c_float,
                                   c_int64, c_int64, c_int64, c_void_p]),
     "pwc_warp_c8_f16": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_int, c_float,

@@ -55,6 +55,11 @@ static constexpr OptDesc kOpts[OPT_COUNT] = {
                                                           // kernel runs (read by the Python engine)
     {"w4_stacked", "PWC_W4_STACKED", 1},                  // F(4x4) rule: maps shorter than a workgroup run as stacked tile groups of several images (dc_conv4's
                                                           // last 32 couts, dc_conv5 on the level-4 lattices); 0 = refused, and the plan keeps the 3-level lattice context
+    {"pyr1_wino", "PWC_PYR1_WINO", 1},                    // fp32 plans: the 16 -> 16 layers of the first pyramid level (conv1aa, conv1b) on the 16-channel F(2x2) kernel
+                                                          // (pwc_pyr1_wino.hip): 1 = layer by layer, 2 = both in one launch (measured slower: opt-in, profiles/r09_pyr1_notes.md),
+                                                          // 0 = the direct MFMA kernel (read by the Python engine when a plan is built, and by pwc_pyr1_wino_preferred)
+    {"pyr1_wino_min_tiles", "PWC_PYR1_WINO_MIN_TILES", 512},   // ... for launches of at least this many 8 x 64 tiles (two workgroups per CU; batch 1 at 448x1024 is 448 tiles and
+                                                          // measured 0.2 % slower on the new kernel, so it keeps the direct one), pwc_pyr1_wino_preferred
 };
 // the table is indexed by enum Opt (pwc_common.h): a row out of order would silently give one switch another's value
 constexpr bool opt_is(Opt o, const char *name) {
@@ -68,7 +73,8 @@ static_assert(opt_is(OPT_CONV_WINO4, "conv_wino4") && opt_is(OPT_W4_TAILSPLIT, "
               opt_is(OPT_CORR_SMALL_TILES, "corr_small_tiles") && opt_is(OPT_HEAD10, "head10") && opt_is(OPT_F16_LEVEL_CORR, "f16_level_corr") &&
               opt_is(OPT_WARPCORR_WINDOW, "warpcorr_window") && opt_is(OPT_STREAM_SLICE_WGS, "stream_slice_wgs") &&
               opt_is(OPT_C1_IN_ARENA, "c1_in_arena") && opt_is(OPT_HEAD_SLICED_MIN_TILES, "head_sliced_min_tiles") &&
-              opt_is(OPT_W4_STACKED, "w4_stacked"), "kOpts rows follow enum Opt");
+              opt_is(OPT_W4_STACKED, "w4_stacked") && opt_is(OPT_PYR1_WINO, "pyr1_wino") &&
+              opt_is(OPT_PYR1_WINO_MIN_TILES, "pyr1_wino_min_tiles"), "kOpts rows follow enum Opt");
 static std::atomic<int> g_opt_val[OPT_COUNT];
 static std::atomic<unsigned char> g_opt_set[OPT_COUNT];
 

@@ -197,6 +197,9 @@ class PwcPlan:
         self.wino_packed: Dict[str, torch.Tensor] = {}
         self.wino4_packed: Dict[str, torch.Tensor] = {}        # F(4x4,3x3) banks, packed on first use by the layers the rule picks
         self.split96_bias: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        # 16 -> 16 layers (conv1aa, conv1b): G g Gt for the 16-channel F(2x2) kernel (pwc_pyr1_wino.hip, 16 KB each, no workspace); option
+        # "pyr1_wino" = 0 when the plan is built keeps them on the direct MFMA kernel
+        self.pyr1_packed: Dict[str, torch.Tensor] = {}
         self.conv_macs = {"direct": 0, "executed": 0}
         self.wino = os.environ.get("PWC_CONV_WINO", "1") != "0" and dtype == torch.float32
         # 0 (environment, or pwc_set_option("conv_wino4", 0) before the plan is built): large layers stay on F(2x2,3x3) (A/B runs, error budget)
@@ -211,6 +214,8 @@ class PwcPlan:
                     # G g Gt for every layer the Winograd route could take (67 MB for the whole net): nothing is allocated later
                     if self.wino and t.shape[0] >= 32 and t.shape[1] >= 16:
                         self.wino_packed[key[:-len(".weight")]] = ops.pack_conv3x3_wino(t)
+                    if self.wino and tuple(t.shape[:2]) == (16, 16) and _lib.get_option("pyr1_wino") > 0:
+                        self.pyr1_packed[key[:-len(".weight")]] = ops.pack_pyr1_wino(t)
             for l in self.head10:
                 w10 = torch.cat((self.p["predict_flow%d.weight" % l], ops.deconv_as_conv3x3(self.p["upfeat%d.weight" % l])), 0)
                 self.p["head10_%d.weight" % l] = w10.contiguous()
@@ -347,6 +352,12 @@ class PwcPlan:
             return
         macs = x.shape[0] * w.shape[0] * w.shape[1] * 9 * ((x.shape[2] - 1) // stride + 1) * ((x.shape[3] - 1) // stride + 1)
         self.conv_macs["direct"] += macs                          # what the layer costs as a direct convolution
+        if (key in self.pyr1_packed and stride == 1 and dilation == 1 and residual is None and act and x.dtype == torch.float32
+                and ops.pyr1_wino_preferred(x.shape[0], x.shape[2], x.shape[3])):
+            # first pyramid level: Winograd F(2x2,3x3) with the whole filter bank in LDS (125 instead of 180 us per layer at batch 16)
+            ops.pyr1_wino(x, self.pyr1_packed[key], b, leaky_slope=LEAKY, out=out)
+            self.conv_macs["executed"] += macs * 16 // 36          # multiplications the matrix cores perform
+            return
         if (self.wino and self.wino4 and key in self.wino_packed and self.conv_backend == "hip" and stride == 1 and dilation == 1 and residual is None
                 and x.dtype == torch.float32 and ops.conv3x3_wino4_preferred(x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[0])):
             # Winograd F(4x4,3x3): 4x fewer multiplications than the direct form for the large, well-filled layers (gated: DESIGN.md 4b)
@@ -374,6 +385,18 @@ class PwcPlan:
             if residual is not None:
                 y = y + residual
             out.copy_(y)
+
+    def _conv16_pair(self, name1: str, name2: str, x: torch.Tensor, out: torch.Tensor) -> bool:
+        """Two consecutive 16 -> 16 layers (conv1aa, conv1b) as one launch where the rule says so; False: the caller runs them one by one"""
+        k1, k2 = name1 + ".0", name2 + ".0"
+        if not (k1 in self.pyr1_packed and k2 in self.pyr1_packed and x.dtype == torch.float32
+                and ops.pyr1_wino_preferred(x.shape[0], x.shape[2], x.shape[3]) == 2):
+            return False
+        macs = 2 * x.shape[0] * 16 * 16 * 9 * x.shape[2] * x.shape[3]
+        self.conv_macs["direct"] += macs
+        self.conv_macs["executed"] += macs * 16 // 36              # the tiles' recomputed ring (1.22x on the first layer) is not counted
+        ops.pyr1_wino_pair(x, self.pyr1_packed[k1], self.p[k1 + ".bias"], self.pyr1_packed[k2], self.p[k2 + ".bias"], leaky_slope=LEAKY, out=out)
+        return True
 
     def _deconv(self, name: str, x: torch.Tensor, out: torch.Tensor) -> None:
         w, b = self.p[name + ".weight"], self.p[name + ".bias"]
@@ -408,6 +431,9 @@ class PwcPlan:
                     self._conv(na, img, first[s0:s1], stride=2)
             else:
                 self._conv(na, prev, first[lo:hi], stride=2)
+            if naa is not None and self._conv16_pair(naa, nb, a, bb):
+                prev = bb                                          # conv1aa + conv1b as one launch, a -> bb (tiles read their neighbours: not in place)
+                continue
             if naa is not None:
                 self._conv(naa, a, bb)
             self._conv(nb, bb, a)
@@ -545,6 +571,7 @@ class PwcPlan:
         tot += sum(t.numel() * t.element_size() for t in self.packed.values())
         tot += sum(t.numel() * t.element_size() for t in self.wino_packed.values())
         tot += sum(t.numel() * t.element_size() for t in self.wino4_packed.values())
+        tot += sum(t.numel() * t.element_size() for t in self.pyr1_packed.values())
         if self.workspace is not None:
             tot += self.workspace.numel() * self.workspace.element_size()
         return tot

@@ -422,6 +422,77 @@ def conv3x3_wino(x: torch.Tensor, upacked: torch.Tensor, bias: torch.Tensor, cou
     return out
 
 
+def pyr1_wino_preferred(B: int, H: int, W: int) -> int:
+    """Route of the 16 -> 16 layers on B images of H x W (option "pyr1_wino"; rule in the library): 0 = conv3x3, 1 = pyr1_wino layer by
+    layer, 2 = two consecutive layers as one pyr1_wino_pair launch."""
+    return int(_lib.load().pwc_pyr1_wino_preferred(B, H, W))
+
+
+def pack_pyr1_wino(weight: torch.Tensor) -> torch.Tensor:
+    """[16,16,3,3] filter bank -> G g Gt in the LDS order of pwc_pyr1_wino_fwd (device, float32, 16 KB)."""
+    lib = _lib.load()
+    if tuple(weight.shape) != (16, 16, 3, 3):
+        raise ValueError("expected [16,16,3,3], got %s" % (tuple(weight.shape),))
+    if not weight.is_cuda:
+        raise PwcHipError("weights must be on the device")
+    w = weight.detach().to(torch.float32).contiguous()
+    up = torch.empty(lib.pwc_pyr1_wino_packed_bytes() // 4, dtype=torch.float32, device=w.device)
+    with torch.cuda.device(w.device):
+        rc = lib.pwc_pyr1_wino_pack(w.data_ptr(), up.data_ptr(), _stream(w))
+    check(rc, "pwc_pyr1_wino_pack")
+    return up
+
+
+def pyr1_wino(x: torch.Tensor, upacked: torch.Tensor, bias: torch.Tensor, leaky_slope: float = 0.1,
+              out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Conv2d(16 -> 16, 3x3, pad 1) + bias + LeakyReLU by Winograd F(2x2,3x3) on the fp32 matrix cores (W % 4 == 0)."""
+    lib = _lib.load()
+    bsx = _plane_dense(x, "x")
+    B, cin, H, W = x.shape
+    if x.dtype != torch.float32 or cin != 16:
+        raise ValueError("pyr1_wino takes float32 [B,16,H,W], got %s %s" % (x.dtype, tuple(x.shape)))
+    if out is None:
+        out = torch.empty((B, 16, H, W), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (B, 16, H, W) or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError("out must be %s, got %s" % ((B, 16, H, W), tuple(out.shape)))
+    bsy = _plane_dense(out, "out")
+    if upacked.dtype != torch.float32 or upacked.numel() * 4 != lib.pwc_pyr1_wino_packed_bytes() or upacked.device != x.device:
+        raise ValueError("packed filters are not those of pack_pyr1_wino")
+    if bias.dtype != torch.float32 or bias.numel() != 16 or bias.device != x.device or not bias.is_contiguous():
+        raise ValueError("bias must be float32[16] on %s" % x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.pwc_pyr1_wino_fwd(x.data_ptr(), upacked.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, float(leaky_slope),
+                                   bsx, bsy, _stream(x))
+    check(rc, "pwc_pyr1_wino_fwd")
+    return out
+
+
+def pyr1_wino_pair(x: torch.Tensor, upacked1: torch.Tensor, bias1: torch.Tensor, upacked2: torch.Tensor, bias2: torch.Tensor,
+                   leaky_slope: float = 0.1, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Two Conv2d(16 -> 16, 3x3, pad 1) + bias + LeakyReLU layers in one launch (the map between them stays in LDS); out is not x."""
+    lib = _lib.load()
+    bsx = _plane_dense(x, "x")
+    B, cin, H, W = x.shape
+    if x.dtype != torch.float32 or cin != 16:
+        raise ValueError("pyr1_wino_pair takes float32 [B,16,H,W], got %s %s" % (x.dtype, tuple(x.shape)))
+    if out is None:
+        out = torch.empty((B, 16, H, W), dtype=x.dtype, device=x.device)
+    elif tuple(out.shape) != (B, 16, H, W) or out.dtype != x.dtype or out.device != x.device:
+        raise ValueError("out must be %s, got %s" % ((B, 16, H, W), tuple(out.shape)))
+    bsy = _plane_dense(out, "out")
+    need = lib.pwc_pyr1_wino_packed_bytes()
+    for up, bias in ((upacked1, bias1), (upacked2, bias2)):
+        if up.dtype != torch.float32 or up.numel() * 4 != need or up.device != x.device:
+            raise ValueError("packed filters are not those of pack_pyr1_wino")
+        if bias.dtype != torch.float32 or bias.numel() != 16 or bias.device != x.device or not bias.is_contiguous():
+            raise ValueError("bias must be float32[16] on %s" % x.device)
+    with torch.cuda.device(x.device):
+        rc = lib.pwc_pyr1_wino_pair_fwd(x.data_ptr(), upacked1.data_ptr(), bias1.data_ptr(), upacked2.data_ptr(), bias2.data_ptr(),
+                                        out.data_ptr(), B, H, W, float(leaky_slope), bsx, bsy, _stream(x))
+    check(rc, "pwc_pyr1_wino_pair_fwd")
+    return out
+
+
 def conv3x3_wino4_preferred(B: int, cin: int, H: int, W: int, cout: int, dilation: int = 1) -> bool:
     """Measured rule: does Winograd F(4x4,3x3) beat F(2x2,3x3) for this layer (large, well-filled maps, dilation 1)?"""
     return bool(_lib.load().pwc_conv3x3_wino4_preferred(B, cin, H, W, cout, dilation))
