@@ -28,6 +28,8 @@
  *   pwc_sup_multiscale_loss_*  supervised_multiscale_loss train2.py:124-167 (all levels in one launch, forward and backward)
  *   pwc_epipolar_*      _flow_to_pairs / _ransac_F / build_epipolar_mask_from_flow / epipolar_sampson_loss
  *                       train_fundamental.py:169-382 (the hard epipolar mask and soft Sampson penalty, :459-483)
+ *   pwc_fb_metrics      _forward_backward_consistency / _oob_ratio train_pseudo.py:178-236, forward_backward_cycle / oob_ratio
+ *                       train_fundamental.py:397-428 (the no-ground-truth validation metrics, on two given flows)
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -320,6 +322,35 @@ int pwc_epipolar_loss_bwd(const void *flow, const void *F, int64_t F_bstride, co
                           const void *mask, int mask_u8, const void *grad_out, void *grad_flow, int B, int H, int W, int robust,
                           double delta, double weight, int64_t flow_bstride, int64_t mask_bstride, void *workspace,
                           int64_t workspace_bytes, void *stream);
+
+/* No-ground-truth validation metrics (ABI v13 additions, csrc/pwc_fb_metrics.hip): forward-backward cycle consistency
+ * (_forward_backward_consistency train_pseudo.py:178-193, forward_backward_cycle train_fundamental.py:397-409) and the
+ * out-of-bounds ratio (_oob_ratio train_pseudo.py:210-236, oob_ratio train_fundamental.py:412-428) in one pass, nothing
+ * image-sized written.  flow12 / flow21 [B,2,h,w] f32 (dense planes, batch strides in elements); flow21 may be NULL.
+ * Per pixel (b, Y, X) of the H x W grid, in fp32 with no fused multiply-add (the arithmetic of pwc_proxy_loss_fwd above):
+ *   1. a = up(flow12)(Y, X):  up(f)(Y, X) = f[Y, X] when (h,w) == (H,W), otherwise
+ *        rh = (float)(h-1) / (float)(H-1);  fy = rh * (float)Y;  y0 = (int)fy;  y1 = y0 + (y0 < h-1);  ly1 = fy - (float)y0;
+ *        ly0 = 1 - ly1  (x alike);  u = ly0 * (lx0 * f00 + lx1 * f01) + ly1 * (lx0 * f10 + lx1 * f11);
+ *        up.x = u * (float)((double)W / w)  (up.y alike with (float)((double)H / h))           -- upsample_flow_to of both scripts;
+ *   2. px = (float)X + a.x;  py = (float)Y + a.y;  the pixel is OUT OF BOUNDS when px < 0 || px > W-1 || py < 0 || py > H-1
+ *        (the pixel form of the scripts' x < -1 | x > 1 | y < -1 | y > 1 on the normalised grid);
+ *   3. ix = min(max(px, 0), W-1);  x0 = floor(ix);  tx = ix - x0;  x1 = min(x0 + 1, W-1)  (y alike);  the four taps are
+ *        v00 = up(flow21)(y0, x0), v01 = up(flow21)(y0, x1), v10 = up(flow21)(y1, x0), v11 = up(flow21)(y1, x1), each evaluated
+ *        from the [h,w] field as in step 1;  wv = (1-ty) * ((1-tx) * v00 + tx * v01) + ty * ((1-tx) * v10 + tx * v11)
+ *        per component -- grid_sample(bilinear, border, align_corners=True) of the scripts' warp / warp_image;
+ *   4. cycle += |a.x + wv.x| + |a.y + wv.y|   (the sum of the two fp32 magnitudes is added in fp64).
+ * out2 (device, float[2]) = {cycle / (B*2*H*W), oob_count / (B*H*W)}; with flow21 == NULL only the count is taken (the scripts'
+ * stand-alone oob_ratio) and out2[0] = 0.  Each 16 x 64 tile leaves {fp64 cycle sum, int64 count} in the workspace, summed in a
+ * fixed tree order, and one final workgroup adds the tiles in order: no atomics, bit-reproducible, no host synchronisation.
+ * workspace: device, 8-byte aligned, pwc_fb_metrics_workspace_bytes(B, H, W) = 16 + 16 bytes per tile (-1 for a non-positive
+ * size).  After the launch its first 16 bytes hold the raw totals: the fp64 cycle sum, then the int64 out-of-bounds count.
+ * PWC_EINVAL, nothing launched: null flow12 / workspace / out2, non-positive sizes, H, W, h or w < 2, H < h, W < w,
+ * B*2*H*W >= 2^31, B > 65535, H > 16 * 65535, a batch stride below 2*h*w, an operand not 4-byte aligned, a workspace that is too
+ * small or not 8-byte aligned. */
+int64_t pwc_fb_metrics_workspace_bytes(int B, int H, int W);
+int pwc_fb_metrics(const void *flow12, const void *flow21, int B, int h, int w, int H, int W,
+                   int64_t flow12_bstride, int64_t flow21_bstride,
+                   void *workspace, int64_t workspace_bytes, void *out2, void *stream);
 
 /* Backward warp of x by (flow_scale * flo): bilinear, zero padding, times the validity mask
  * [sum of in-bounds bilinear weights >= mask_threshold]  (PWCNet.py:141-177).

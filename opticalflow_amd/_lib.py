@@ -63,6 +63,8 @@ SIGNATURES = {
                                     + [c_double, c_float, c_float] + [c_int64] * 3 + [c_void_p, c_int64, c_void_p]),
     "pwc_sup_multiscale_loss_bwd": (c_int, [c_void_p] * 4 + [c_int] + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 + [c_int] * 3
                                     + [c_double, c_float, c_float] + [c_int64] * 3 + [c_void_p, c_int64, c_void_p]),
+    "pwc_fb_metrics_workspace_bytes": (c_int64, [c_int] * 3),
+    "pwc_fb_metrics": (c_int, [c_void_p, c_void_p] + [c_int] * 5 + [c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p]),
     "pwc_epipolar_pairs": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p] + [c_int] * 4 + [c_int64] * 2 + [c_void_p]),
     "pwc_epipolar_ransac_workspace_bytes": (c_int64, [c_int, c_int]),
     "pwc_epipolar_ransac": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_int64, c_int, c_int, c_double] + [c_void_p] * 5

@@ -44,6 +44,7 @@
 // No atomics on floats: every result is bit-reproducible.  The mask count of the backward is an integer sum (one 64-bit integer
 // atomic per workgroup; integer addition is associative).
 #include "pwc_common.h"
+#include "pwc_flow_up.h"
 
 namespace {
 
@@ -76,20 +77,7 @@ Geo make_geo(int B, int C, int H, int W, int h, int w, int64_t bs_f, int64_t bs_
     return g;
 }
 
-// upsampled flow (u, v) at full-resolution pixel (Y, X); f = flow of this image ([2][h][w])
-__device__ __forceinline__ float2 up_flow(const float *f, const Geo &g, int Y, int X) {
-    if (g.same) return make_float2(f[(int64_t)Y * g.W + X], f[(int64_t)g.H * g.W + (int64_t)Y * g.W + X]);
-    const float fy = g.rh * (float)Y, fx = g.rw * (float)X;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < g.h - 1 ? 1 : 0), x1 = x0 + (x0 < g.w - 1 ? 1 : 0);
-    const float ly1 = fy - (float)y0, lx1 = fx - (float)x0;
-    const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-    const float *fu = f, *fv = f + (int64_t)g.h * g.w;
-    const int a = y0 * g.w, b = y1 * g.w;
-    const float u = ly0 * (lx0 * fu[a + x0] + lx1 * fu[a + x1]) + ly1 * (lx0 * fu[b + x0] + lx1 * fu[b + x1]);
-    const float v = ly0 * (lx0 * fv[a + x0] + lx1 * fv[a + x1]) + ly1 * (lx0 * fv[b + x0] + lx1 * fv[b + x1]);
-    return make_float2(u * g.sx, v * g.sy);
-}
+using pwc::up_flow;   // pwc_flow_up.h: upsampled flow (u, v) at full-resolution pixel (Y, X)
 
 struct Sample {
     float ix, iy;   // clamped sample point

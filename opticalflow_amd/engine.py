@@ -115,8 +115,8 @@ class PwcPlan:
         for l in range(1, 7):
             h, w = self.size[l]
             c = PYRAMID_CH[l]
-            self.pyr_a[l] = torch.empty((self._slots(B), c, h, w), **kw)      # levels 2-5: replaced by a view of the arena below
-            self.pyr_b[l] = torch.empty((self._slots(B), c, h, w), **kw)
+            self.pyr_a[l] = torch.empty((self._level_slots(B, l), c, h, w), **kw)      # levels 2-5: replaced by a view of the arena below
+            self.pyr_b[l] = torch.empty((self._level_slots(B, l), c, h, w), **kw)
         self.warped = {l: torch.empty((B, PYRAMID_CH[l], *self.size[l]), **kw) for l in range(2, 6)}
         self.arena = {}
         self.arena_base = {}                    # first channel after the dense-block outputs
@@ -311,6 +311,10 @@ class PwcPlan:
     @staticmethod
     def _slots(B: int) -> int:
         return 2 * B
+
+    def _level_slots(self, B: int, level: int) -> int:
+        """batch slots of level `level`'s two pyramid buffers (a plan may need fewer where no decoder level reads them)"""
+        return self._slots(B)
 
     @staticmethod
     def _pair_views(buf: torch.Tensor, B: int):
@@ -629,3 +633,57 @@ class PwcVideoPlan(PwcPlan):
 
     def run(self, x):
         raise RuntimeError("PwcVideoPlan is driven by prime()/push(), not run()")
+
+
+class PwcBidirPlan(PwcPlan):
+    """Both flow directions of B pairs from ONE pyramid pass over their 2B images: ``run(img1, img2) -> (flow12, flow21)`` with
+    flow12 = net(cat(img1, img2)) and flow21 = net(cat(img2, img1)) (the two forwards of the scripts' cycle-consistency check,
+    train_pseudo.py:178-193 / train_fundamental.py:397-409, which run six pyramids over two distinct images).
+
+    Layout: 3B pyramid slots [img1 | img2 | copy of img1's levels 2..6] and ONE decoder pass at batch 2B.  The decoder's
+    first-image features are the view [0:2B] = (img1, img2), its second-image features the overlapping view [B:3B] =
+    (img2, img1), as PwcVideoPlan overlaps [0:B] / [1:B+1]: items 0..B-1 decode the pairs (img1, img2), items B..2B-1 the pairs
+    (img2, img1).  Every image passes conv1a..conv6b exactly once (slots [0,2B)); the third block is a device copy of B sets of
+    level features.  With 3B slots for a 2B decoder c1_in_arena switches itself off, so the decoder copies c1 into its arena
+    as for the video plan.  The base class is built for the DECODER batch 2B; its kernels, packed filters and workspace are
+    PwcPlan's."""
+
+    def __init__(self, params, B, H, W, device, dtype=torch.float32, md=4, normalize_corr=False,
+                 align_corners=False, conv_backend="hip", variant="dc"):
+        self.pairs = int(B)
+        super().__init__(params, 2 * B, H, W, device, dtype, md, normalize_corr, align_corners, conv_backend, variant)
+
+    @staticmethod
+    def _slots(B2: int) -> int:
+        return B2 + B2 // 2                     # B2 = 2B decoder items -> 3B pyramid slots
+
+    def _level_slots(self, B2: int, level: int) -> int:
+        # level 1 feeds only the pyramid (no decoder level reads it): the third block of slots would never be touched there
+        return B2 if level == 1 else self._slots(B2)
+
+    @staticmethod
+    def _pair_views(buf: torch.Tensor, B2: int):
+        return buf[:B2], buf[B2 // 2:]
+
+    def _launch_geometries(self, B2: int, trunk2: bool):
+        # the pyramid runs on 2B = B2 images, not on all 3B slots: the shared scratch has to cover those launches too
+        out = super()._launch_geometries(B2, trunk2)
+        for l in range(1, 7):
+            h, w = self.size[l]
+            for n in self.pyramid_names[l - 1][1:]:
+                if n is not None:
+                    out.append((B2, PYRAMID_CH[l], h, w, PYRAMID_CH[l], 1))
+        return out
+
+    def run(self, img1: torch.Tensor, img2: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        B = self.pairs
+        for name, t in (("img1", img1), ("img2", img2)):
+            if t is None or tuple(t.shape) != (B, 3, self.H, self.W) or t.dtype != self.dtype or t.device != self.device:
+                raise ValueError("plan built for two %s %s images on %s, got %s: %s" % (
+                    (B, 3, self.H, self.W), self.dtype, self.device, name, None if t is None else (tuple(t.shape), t.dtype, t.device)))
+        self.conv_macs = {"direct": 0, "executed": 0}
+        self._pyramid([(ops.densify(img1), 0, B), (ops.densify(img2), B, 2 * B)], 0, 2 * B)
+        for l in range(2, 7):
+            self.pyr_a[l][2 * B:].copy_(self.pyr_a[l][:B])
+        out = self._decode()
+        return out[:B], out[B:]

@@ -857,6 +857,62 @@ class ProxyLossFunction(torch.autograd.Function):
         return gf, None, None, None, None, None, None
 
 
+# ---------------------------------------------------------------- no-ground-truth validation metrics (train_pseudo / train_fundamental)
+def fb_metrics_supported(flow12: torch.Tensor, flow21: Optional[torch.Tensor], H: int, W: int) -> bool:
+    """Python mirror of the placement / geometry rules under which pwc_fb_metrics launches (include/pwc_hip.h): ROCm device
+    tensors of one [B,2,h,w] shape, 2 <= h <= H, 2 <= w <= W, B*2*H*W < 2^31, B <= 65535.  The dtype is the caller's business
+    (the kernel takes float32)."""
+    if not flow12.is_cuda or flow12.dim() != 4 or flow12.shape[1] != 2:
+        return False
+    if flow21 is not None and (not flow21.is_cuda or flow21.shape != flow12.shape or flow21.device != flow12.device):
+        return False
+    B, _, h, w = flow12.shape
+    return 2 <= h <= H and 2 <= w <= W and B * 2 * H * W < 2 ** 31 and 1 <= B <= 65535 and (H + 15) // 16 <= 65535
+
+
+def fb_metrics_workspace_bytes(B: int, H: int, W: int) -> int:
+    n = _lib.load().pwc_fb_metrics_workspace_bytes(B, H, W)
+    if n < 0:
+        raise ValueError("bad fb-metrics geometry")
+    return int(n)
+
+
+def fb_metrics(flow12: torch.Tensor, flow21: Optional[torch.Tensor], H: int, W: int, out: Optional[torch.Tensor] = None,
+               raw: bool = False):
+    """float32 [2] = (cycle, oob) of pwc_fb_metrics: mean |up(flow12) + warp(up(flow21), up(flow12))| over [B,2,H,W] (the scripts'
+    forward-backward cycle) and the fraction of the B*H*W sample points x + up(flow12) that leave the image.  flow12 / flow21
+    float32 [B,2,h,w] with 2 <= h <= H, 2 <= w <= W; flow21 = None: the out-of-bounds ratio alone (cycle is written as 0).
+    One launch pair, no host synchronisation, bit-reproducible.  raw=True returns (out, cycle_sum, oob_count): the float64 sum
+    and the int64 count the two ratios were formed from, as 0-dim device tensors."""
+    lib = _lib.load()
+    flow12 = densify(flow12)
+    B, _, h, w = flow12.shape
+    dev = flow12.device
+    flows = [("flow12", flow12)]
+    if flow21 is not None:
+        flow21 = densify(flow21)
+        flows.append(("flow21", flow21))
+    for name, t in flows:
+        if tuple(t.shape) != (B, 2, h, w) or t.dtype != torch.float32 or t.device != dev:
+            raise ValueError("%s must be float32 %s on %s, got %s %s" % (name, (B, 2, h, w), dev, t.dtype, tuple(t.shape)))
+    bs12 = _plane_dense(flow12, "flow12")
+    bs21 = _plane_dense(flow21, "flow21") if flow21 is not None else 0
+    if out is None:
+        out = torch.empty(2, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (2,) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 [2] tensor on %s" % dev)
+    H, W = int(H), int(W)
+    with torch.cuda.device(dev):
+        nb = fb_metrics_workspace_bytes(B, max(H, 1), max(W, 1))
+        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+        rc = lib.pwc_fb_metrics(flow12.data_ptr(), flow21.data_ptr() if flow21 is not None else None, B, h, w, H, W, bs12, bs21,
+                                ws.data_ptr(), nb, out.data_ptr(), _stream(flow12))
+    check(rc, "pwc_fb_metrics")
+    if raw:
+        return out, ws[:1].view(torch.float64)[0], ws[1]
+    return out
+
+
 # ---------------------------------------------------------------- supervised flow losses (train.py / train2.py)
 SUP_MAX_LEVELS = 8
 MASK_RULES = {"threshold": 0, "raw": 1}   # MaskedCharbonnier's [m > 0.5] / max(sum, 1); compute_epe's raw m / (sum + 1e-8)

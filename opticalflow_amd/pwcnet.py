@@ -41,7 +41,7 @@ import torch.nn as nn
 from . import ops
 from ._lib import PwcHipError
 from .correlation import Correlation, onnx_correlation_enabled
-from .engine import (CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PYRAMID_NAMES, PYRAMID_NAMES_OLD, WARP_SCALE, PwcPlan,
+from .engine import (CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PYRAMID_NAMES, PYRAMID_NAMES_OLD, WARP_SCALE, PwcBidirPlan, PwcPlan,
                      level_in_channels)
 from .weights import load_checkpoint, synthetic_state_dict
 
@@ -241,23 +241,33 @@ class PWCDCNet(nn.Module):
         self._versions = None
         self._param_list = None
 
-    def _plan_for(self, x) -> PwcPlan:
+    def _cached_plan(self, key, device, build):
+        """The plan cached under `key`, built by build(params) from the current weights when it is missing.  Drops every plan first
+        when a parameter was updated in place since the last call; keeps at most `max_cached_plans`, least recently used first."""
         ver = self._param_versions()
         if ver != self._versions:
             self.invalidate_plans()
             self._versions = ver
-        key = self._key(x)
         plan = self._plans.get(key)
         if plan is not None:
             self._plans.move_to_end(key)
-        if plan is None:
-            params = {k: v.detach() for k, v in self.state_dict(keep_vars=True).items()}
-            for k, v in params.items():
-                if v.device != x.device:
-                    raise PwcHipError("parameter %s is on %s but the input is on %s: call net.to(device) first"
-                                      % (k, v.device, x.device))
-                if v.dtype != torch.float32:
-                    raise NotImplementedError("parameters must be float32 (got %s for %s)" % (v.dtype, k))
+            return plan
+        params = {k: v.detach() for k, v in self.state_dict(keep_vars=True).items()}
+        for k, v in params.items():
+            if v.device != device:
+                raise PwcHipError("parameter %s is on %s but the input is on %s: call net.to(device) first"
+                                  % (k, v.device, device))
+            if v.dtype != torch.float32:
+                raise NotImplementedError("parameters must be float32 (got %s for %s)" % (v.dtype, k))
+        plan = build(params)
+        self._plans[key] = plan
+        while len(self._plans) > max(1, int(self.max_cached_plans)):
+            old, _ = self._plans.popitem(last=False)
+            self._graphs.pop(old, None)
+        return plan
+
+    def _plan_for(self, x) -> PwcPlan:
+        def build(params):
             if self.precision in ("fp16", "fp16-strict"):
                 if self.conv_backend != "hip" or x.dtype != torch.float32:
                     raise NotImplementedError("precision='%s' is built for conv_backend='hip' and float32 input" % self.precision)
@@ -265,16 +275,45 @@ class PWCDCNet(nn.Module):
                     from .engine_f16 import PwcPlanF16 as Plan16
                 else:
                     from .engine_strict import PwcPlanStrict as Plan16
-                plan = Plan16(params, x.shape[0], x.shape[2], x.shape[3], x.device, self.md,
+                return Plan16(params, x.shape[0], x.shape[2], x.shape[3], x.device, self.md,
                               self._normalize_now(), self.align_corners, self.variant)
-            else:
-                plan = PwcPlan(params, x.shape[0], x.shape[2], x.shape[3], x.device, x.dtype, self.md,
-                               self._normalize_now(), self.align_corners, self.conv_backend, self.variant)
-            self._plans[key] = plan
-            while len(self._plans) > max(1, int(self.max_cached_plans)):
-                old, _ = self._plans.popitem(last=False)
-                self._graphs.pop(old, None)
-        return plan
+            return PwcPlan(params, x.shape[0], x.shape[2], x.shape[3], x.device, x.dtype, self.md,
+                           self._normalize_now(), self.align_corners, self.conv_backend, self.variant)
+
+        return self._cached_plan(self._key(x), x.device, build)
+
+    # ---- both directions of a batch from one pyramid pass ---------------------------------------
+    def _pair_key(self, img1: torch.Tensor):
+        """Cache key of the bidirectional plan: _key's fields (the effective normalisation included) behind a tag no PwcPlan key
+        carries, so a forward of the same batch and size never finds this plan and vice versa."""
+        return ("bidir",) + self._key(img1)
+
+    def _shares_pyramid(self, img1: torch.Tensor, img2: torch.Tensor) -> bool:
+        return bool(self.precision == "fp32" and img1.is_cuda and img2.is_cuda and img1.dtype == torch.float32
+                    and not onnx_correlation_enabled())
+
+    def flow_pair(self, img1: torch.Tensor, img2: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+        """``(flow12, flow21)`` = ``(net(cat(img1, img2)), net(cat(img2, img1)))`` as eval-mode flows [B,2,H/4,W/4], built without
+        autograd (as the scripts' ``@torch.no_grad()`` consistency checks call the model).  fp32 models on a ROCm device run
+        engine.PwcBidirPlan: each of the 2B images passes the feature pyramid once and one decoder pass at batch 2B gives both
+        directions; the plan lives in the model's plan cache, so a call after ``optimizer.step()`` rebuilds it from the updated
+        weights.  ``precision="fp16"`` / ``"fp16-strict"`` models, CPU models and USE_ONNX_CORRELATION take two ordinary
+        forwards: the same result, without the sharing.  ``use_graph`` does not apply to the shared-pyramid plan."""
+        if img1.dim() != 4 or img1.shape[1] != 3 or img1.shape != img2.shape:
+            raise ValueError("expected two [B,3,H,W] image batches of one shape, got %s and %s" % (tuple(img1.shape), tuple(img2.shape)))
+        if not self._shares_pyramid(img1, img2):
+            training, self.training = self.training, False          # the eval-mode flow2, whatever mode the caller is in
+            try:
+                with torch.no_grad():
+                    return self(torch.cat((img1, img2), 1)), self(torch.cat((img2, img1), 1))
+            finally:
+                self.training = training
+        with torch.no_grad():
+            plan = self._cached_plan(self._pair_key(img1), img1.device, lambda params: PwcBidirPlan(
+                params, img1.shape[0], img1.shape[2], img1.shape[3], img1.device, img1.dtype, self.md,
+                self._normalize_now(), self.align_corners, self.conv_backend, self.variant))
+            f12, f21 = plan.run(img1, img2)
+            return f12.clone(), f21.clone()
 
     def _run_graph(self, key, plan: PwcPlan, x: torch.Tensor) -> torch.Tensor:
         entry = self._graphs.get(key)
