@@ -60,6 +60,20 @@ def old_variant_perm(k: int, od: int) -> torch.Tensor:
     return torch.cat([torch.arange(start[n], start[n] + sizes[n]) for n in physical])
 
 
+def reorder_old_variant(p: Dict[str, torch.Tensor], nd: int = 81) -> None:
+    """PWCDCNet_old's filters in `p`: input channels from the reference's concatenation order to the arena's (old_variant_perm)"""
+    for l in range(2, 7):
+        od = level_in_channels(l, nd)
+        names = [("conv%d_%d.0.weight" % (l, k), k, 1) for k in range(1, 5)] + [("predict_flow%d.weight" % l, 5, 1)]
+        names.append(("upfeat%d.weight" % l, 5, 0) if l > 2 else ("dc_conv1.0.weight", 5, 1))
+        for key, k, dim in names:
+            p[key] = p[key].index_select(dim, old_variant_perm(k, od).to(p[key].device)).contiguous()
+
+
+# multiplications a route executes per multiplication of the direct form, as (numerator, denominator)
+ROUTE_MACS = {"pyr1": (16, 36), "pyr1x2": (16, 36), "wino4": (36, 144), "wino2": (16, 36), "direct": (1, 1), "torch": (1, 1)}
+
+
 def level_in_channels(level: int, nd: int = 81) -> int:
     """`od` of PWCNet.py:77,87,97,107,117."""
     return nd if level == 6 else nd + PYRAMID_CH[level] + 4
@@ -95,19 +109,15 @@ class PwcPlan:
         self.mask_threshold = 0.9999 if variant == "dc" else 0.999        # PWCNet.py:174 / :400
         self.p = dict(params)
         if variant == "old":
-            # re-order the filters' input channels from the reference's concatenation order to the arena's
-            for l in range(2, 7):
-                od = level_in_channels(l, self.nd)
-                names = [("conv%d_%d.0.weight" % (l, k), k, 1) for k in range(1, 5)]
-                names.append(("predict_flow%d.weight" % l, 5, 1))
-                if l > 2:
-                    names.append(("upfeat%d.weight" % l, 5, 0))
-                else:
-                    names.append(("dc_conv1.0.weight", 5, 1))
-                for key, k, dim in names:
-                    perm = old_variant_perm(k, od).to(device)
-                    self.p[key] = self.p[key].index_select(dim, perm).contiguous()
+            reorder_old_variant(self.p, self.nd)
         kw = dict(device=device, dtype=dtype)
+        # The switches every convolution's route depends on, read ONCE: a plan fixes its routes when it is built (_route), as a
+        # captured graph does.  conv_wino4 = 0 (environment, or pwc_set_option("conv_wino4", 0) before the plan is built): large
+        # layers stay on F(2x2,3x3) (A/B runs, error budget); pyr1_wino = 0 keeps the 16 -> 16 layers on the direct MFMA kernel
+        hip = conv_backend == "hip"
+        self.wino = os.environ.get("PWC_CONV_WINO", "1") != "0"
+        self.wino4 = os.environ.get("PWC_CONV_WINO4", "1") != "0" and (not hip or _lib.get_option("conv_wino4") != 0)
+        self.pyr1_wino = bool(hip and self.wino and _lib.get_option("pyr1_wino") > 0)
 
         self.size = {l: (H >> l, W >> l) for l in range(1, 7)}
         # pyramid scratch: per level two ping-pong buffers for the 2B batch, plus c2 (second image)
@@ -170,143 +180,71 @@ class PwcPlan:
         # One level deeper (ctx_lattice4): dc_conv4 runs all 96 couts on F(4x4) and stores ITS result as lattices too, so dc_conv5 is a
         # dilation-1 F(4x4) layer on 256B images of h/16 x w/16 (7x16 at 448x1024) -- both on the stacked tile groups of
         # pwc_conv_wino4.hip (several short images per workgroup), where the rule takes them; option "w4_stacked" = 0 restores the 3-level form.
-        wino_on = (os.environ.get("PWC_CONV_WINO", "1") != "0" and os.environ.get("PWC_CONV_WINO4", "1") != "0"
-                   and (conv_backend != "hip" or _lib.get_option("conv_wino4") != 0))
         self.ctx_lattice = bool(
-            trunk2 and conv_backend == "hip" and dtype == torch.float32 and wino_on and os.environ.get("PWC_CTX_LATTICE", "1") != "0"
+            trunk2 and hip and self.wino and self.wino4 and os.environ.get("PWC_CTX_LATTICE", "1") != "0"
             and h2 % 8 == 0 and w2 % 32 == 0
             and ops.conv3x3_wino4_preferred(B, level_in_channels(2, self.nd) + DENSE_TOTAL, h2, w2, CONTEXT[0][0])
             and ops.conv3x3_wino4_preferred(4 * B, CONTEXT[0][0], h2 // 2, w2 // 2, CONTEXT[1][0])
             and ops.conv3x3_wino4_preferred(16 * B, CONTEXT[1][0], h2 // 4, w2 // 4, CONTEXT[2][0]))
-        self.ctx_lattice4 = False
+        self.ctx_lattice4 = self.dc4_split = False
+        self.ctx4_lat: Optional[torch.Tensor] = None
         if self.ctx_lattice:
             self.ctx[0] = torch.empty((4 * B, CONTEXT[0][0], h2 // 2, w2 // 2), **kw)
             self.ctx[1] = torch.empty((16 * B, CONTEXT[1][0], h2 // 4, w2 // 4), **kw)
             self.ctx[2] = torch.empty((64 * B, CONTEXT[2][0], h2 // 8, w2 // 8), **kw)
+            w4 = self.p["dc_conv4.0.weight"]
             self.ctx_lattice4 = bool(
                 h2 % 16 == 0 and w2 % 64 == 0
-                and tuple(self.p["dc_conv4.0.weight"].shape[:2]) == (CONTEXT[3][0], CONTEXT[2][0])
+                and tuple(w4.shape[:2]) == (CONTEXT[3][0], CONTEXT[2][0])
                 and tuple(self.p["dc_conv5.0.weight"].shape[:2]) == (CONTEXT[4][0], CONTEXT[3][0])
                 and ops.conv3x3_wino4_preferred(64 * B, CONTEXT[2][0], h2 // 8, w2 // 8, CONTEXT[3][0])
                 and ops.conv3x3_wino4_preferred(256 * B, CONTEXT[3][0], h2 // 16, w2 // 16, CONTEXT[4][0]))
+            # dc_conv4 (128 -> 96 on 64B images of h/8 x w/8, e.g. 14x32): its first 64 couts fill F(4x4)'s 32-column tile
+            # groups, a 32-cout F(4x4) launch (32-row workgroups) would be half empty -> those couts stay on F(2x2).  A decision of
+            # its own, not _split96_wanted: it asks neither for F(4x4)'s no to all 96 couts nor for F(2x2)'s yes to the last 32
+            self.dc4_split = bool(not self.ctx_lattice4 and w4.shape[0] == 96
+                                  and ops.conv3x3_wino4_preferred(64 * B, w4.shape[1], h2 // 8, w2 // 8, 64))
             n4, s4 = (256 * B, 16) if self.ctx_lattice4 else (64 * B, 8)      # images / size divisor of dc_conv4's output and dc_conv5
             self.ctx[3] = torch.empty((n4, CONTEXT[3][0], h2 // s4, w2 // s4), **kw)
             self.ctx4_lat = torch.empty((n4, CONTEXT[4][0], h2 // s4, w2 // s4), **kw)
+        for l in self.head10:
+            w10 = torch.cat((self.p["predict_flow%d.weight" % l], ops.deconv_as_conv3x3(self.p["upfeat%d.weight" % l])), 0)
+            self.p["head10_%d.weight" % l] = w10.contiguous()
+            self.p["head10_%d.bias" % l] = torch.cat((self.p["predict_flow%d.bias" % l],
+                                                       self.p["upfeat%d.bias" % l].repeat_interleave(4))).contiguous()
 
+        # Filter banks in each kernel family's own order, packed by _route for the launches that take that family: direct MFMA,
+        # G g Gt of F(2x2,3x3), of F(4x4,3x3) (4x the filter bytes), and of the 16-channel F(2x2) kernel (pwc_pyr1_wino.hip, 16 KB each)
         self.packed: Dict[str, torch.Tensor] = {}
         self.wino_packed: Dict[str, torch.Tensor] = {}
-        self.wino4_packed: Dict[str, torch.Tensor] = {}        # F(4x4,3x3) banks, packed on first use by the layers the rule picks
-        self.split96_bias: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
-        # 16 -> 16 layers (conv1aa, conv1b): G g Gt for the 16-channel F(2x2) kernel (pwc_pyr1_wino.hip, 16 KB each, no workspace); option
-        # "pyr1_wino" = 0 when the plan is built keeps them on the direct MFMA kernel
+        self.wino4_packed: Dict[str, torch.Tensor] = {}
         self.pyr1_packed: Dict[str, torch.Tensor] = {}
+        self.split96_bias: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        self.routes: Dict[tuple, str] = {}                     # (layer, geometry, ...) -> route, see _route
         self.conv_macs = {"direct": 0, "executed": 0}
-        self.wino = os.environ.get("PWC_CONV_WINO", "1") != "0" and dtype == torch.float32
-        # 0 (environment, or pwc_set_option("conv_wino4", 0) before the plan is built): large layers stay on F(2x2,3x3) (A/B runs, error budget)
-        self.wino4 = os.environ.get("PWC_CONV_WINO4", "1") != "0" and (conv_backend != "hip" or _lib.get_option("conv_wino4") != 0)
+        # ONE scratch shared by every convolution of the plan (they run back to back on one stream): split-K of the direct and
+        # F(2x2) kernels, tail / whole-launch split of F(4x4), Cin slices of the streaming head.  pwc_conv3x3_wino*_preferred count
+        # those splits, so the buffer has to cover EVERY launch the plan makes (a hand-written list of geometries had
+        # missed the lattice layers and the pyramid; the C side then quietly ran unsplit).  Hence no list: the plan walks its own
+        # forward once with `planning` set -- every launch site resolves its route, packs that route's bank, raises workspace_need
+        # to that kernel's demand and returns without launching -- and allocates the scratch afterwards.
+        self.workspace_need = 0
         self.workspace: Optional[torch.Tensor] = None
-        if conv_backend == "hip":
-            for key, t in self.p.items():
-                if not trunk2 and key.startswith(("conv2_", "predict_flow2", "dc_conv")):
-                    continue                                   # run by the caller (engine_strict) in its own format
-                if key.endswith(".weight") and t.dim() == 4 and t.shape[2:] == (3, 3):
-                    self.packed[key[:-len(".weight")]] = ops.pack_conv3x3(t)
-                    # G g Gt for every layer the Winograd route could take (67 MB for the whole net): nothing is allocated later
-                    if self.wino and t.shape[0] >= 32 and t.shape[1] >= 16:
-                        self.wino_packed[key[:-len(".weight")]] = ops.pack_conv3x3_wino(t)
-                    if self.wino and tuple(t.shape[:2]) == (16, 16) and _lib.get_option("pyr1_wino") > 0:
-                        self.pyr1_packed[key[:-len(".weight")]] = ops.pack_pyr1_wino(t)
-            for l in self.head10:
-                w10 = torch.cat((self.p["predict_flow%d.weight" % l], ops.deconv_as_conv3x3(self.p["upfeat%d.weight" % l])), 0)
-                self.p["head10_%d.weight" % l] = w10.contiguous()
-                self.p["head10_%d.bias" % l] = torch.cat((self.p["predict_flow%d.bias" % l],
-                                                           self.p["upfeat%d.bias" % l].repeat_interleave(4))).contiguous()
-                self.packed["head10_%d" % l] = ops.pack_conv3x3(self.p["head10_%d.weight" % l])
-            # F(4x4,3x3) banks for the layers the measured rule picks at THIS geometry (4x the filter bytes each): packed now, so that a
-            # run never allocates (the lazy path in _conv only serves callers that drive _conv with other shapes, e.g. bench probes)
-            if self.wino and self.wino4:
-                geo = []
-                for l in range(2, 7):
-                    for n in self.pyramid_names[l - 1][1:]:
-                        if n is not None:
-                            geo.append((n + ".0", self._slots(B), PYRAMID_CH[l], PYRAMID_CH[l], l))
-                for l in range(2 if trunk2 else 3, 7):
-                    cin = level_in_channels(l, self.nd)
-                    for i, co in enumerate(DENSE_OUT):
-                        geo.append(("conv%d_%d.0" % (l, i), B, cin, co, l))
-                        cin += co
-                if trunk2:
-                    cin = level_in_channels(2, self.nd) + DENSE_TOTAL
-                    for i, (co, dil) in enumerate(CONTEXT):
-                        if dil == 1:
-                            geo.append(("dc_conv%d.0" % (i + 1), B, cin, co, 2))
-                        cin = co
-                    if self.ctx_lattice:                      # dc_conv2 / dc_conv3 run as dilation-1 layers on the lattices
-                        for key in ("dc_conv2.0", "dc_conv3.0") + (("dc_conv4.0", "dc_conv5.0") if self.ctx_lattice4 else ()):
-                            self.wino4_packed[key] = ops.pack_conv3x3_wino4(self.p[key + ".weight"])
-                        # dc_conv4 (128 -> 96 on 64B images of h/8 x w/8, e.g. 14x32): its first 64 couts fill F(4x4)'s 32-column tile
-                        # groups, a 32-cout F(4x4) launch (32-row workgroups) would be half empty -> those couts stay on F(2x2)
-                        w4 = self.p["dc_conv4.0.weight"]
-                        self.dc4_split = bool(not self.ctx_lattice4 and w4.shape[0] == 96
-                                              and ops.conv3x3_wino4_preferred(64 * B, w4.shape[1], h2 // 8, w2 // 8, 64))
-                        if self.dc4_split:
-                            self._pack_split96("dc_conv4.0")
-                for key, b_, cin, co, l in geo:
-                    h, w = self.size[l]
-                    if key in self.wino_packed and ops.conv3x3_wino4_preferred(b_, cin, h, w, co):
-                        self.wino4_packed[key] = ops.pack_conv3x3_wino4(self.p[key + ".weight"])
-                    elif key in self.wino_packed and self._split96_wanted(b_, cin, h, w, co):
-                        self._pack_split96(key)
-            # ONE scratch shared by every convolution of the plan (they run back to back on one stream): split-K of the direct and
-            # F(2x2) kernels, tail / whole-launch split of F(4x4).  pwc_conv3x3_wino*_preferred count those splits, so the buffer has to
-            # cover EVERY launch the plan can make -- decoder, pyramid (2B images), context layers in NCHW and in the lattice-major
-            # layout (the lattice geometries and the pyramid were missing; the C side then quietly ran unsplit).
-            self.workspace_need = self._workspace_bytes(B, trunk2)
-            need = self.workspace_need
-            if need:
-                self.workspace = torch.empty((need // 4,), **kw)
+        self.planning = True
+        self._plan_launches()
+        self.planning = False
+        if self.workspace_need:
+            self.workspace = torch.empty((self.workspace_need // 4,), **kw)
 
-    def _launch_geometries(self, B: int, trunk2: bool):
-        """(images, cin, h, w, cout, dilation) of every 3x3 stride-1 convolution this plan can launch"""
-        out = []
-        for l in range(1, 7):                                  # pyramid: the stride-1 layers of each level on both images
-            h, w = self.size[l]
-            for n in self.pyramid_names[l - 1][1:]:
-                if n is not None:
-                    out.append((self._slots(B), PYRAMID_CH[l], h, w, PYRAMID_CH[l], 1))
-        for l in range(2 if trunk2 else 3, 7):                 # dense blocks + flow heads
-            h, w = self.size[l]
-            cin = level_in_channels(l, self.nd)
-            for co in DENSE_OUT + (2, 10):                     # 10: flow head + upfeat phases as one convolution (small levels)
-                out.append((B, cin, h, w, co, 1))
-                out.append((B, cin, h, w, min(co, 64), 1))     # the F(4x4) part of a 96-cout layer run as 64 + 32
-                cin += co if co not in (2, 10) else 0
-        if trunk2:
-            h, w = self.size[2]
-            cin = level_in_channels(2, self.nd) + DENSE_TOTAL
-            for co, dil in CONTEXT:
-                out.append((B, cin, h, w, co, dil))
-                cin = co
-            if getattr(self, "ctx_lattice", False):            # the same layers on their pixel lattices (see __init__)
-                c = [co for co, _ in CONTEXT]
-                out += [(4 * B, c[0], h // 2, w // 2, c[1], 1), (16 * B, c[1], h // 4, w // 4, c[2], 1),
-                        (64 * B, c[2], h // 8, w // 8, c[3], 1), (64 * B, c[2], h // 8, w // 8, 64, 1), (64 * B, c[2], h // 8, w // 8, 32, 1),
-                        (64 * B, c[3], h // 8, w // 8, c[4], 2)]
-                if getattr(self, "ctx_lattice4", False):       # dc_conv5 as a dilation-1 layer on the level-4 lattices
-                    out.append((256 * B, c[3], h // 16, w // 16, c[4], 1))
-        return out
+    def _images(self, n: int) -> torch.Tensor:
+        """shape-only stand-in for n input images (planning launches nothing)"""
+        return torch.empty((n, 3, self.H, self.W), device="meta")
 
-    def _workspace_bytes(self, B: int, trunk2: bool) -> int:
-        need = 0
-        for n, cin, h, w, co, dil in self._launch_geometries(B, trunk2):
-            need = max(need, ops.conv3x3_workspace_bytes(n, cin, h, w, co, 1, dil))
-            if co == 2 and dil == 1:                            # predict_flowL + upfeatL as one streaming pass, cut along Cin when small
-                need = max(need, ops.head_upfeat_workspace_bytes(n, cin, h, w))
-            if self.wino and co >= 32 and dil <= 8:
-                need = max(need, ops.conv3x3_wino_workspace_bytes(n, cin, h, w, co, dil))
-            if self.wino and self.wino4 and co >= 32 and dil == 1 and w % 4 == 0:
-                need = max(need, ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, co))
-        return need
+    def _plan_launches(self) -> None:
+        """what run() launches"""
+        B = self.B
+        self._pyramid([(self._images(B), 0, B), (self._images(B), B, 2 * B)], 0, 2 * B)
+        self._decode()
 
     @staticmethod
     def _slots(B: int) -> int:
@@ -337,6 +275,9 @@ class PwcPlan:
         self.split96_bias[key] = (b[:64].contiguous(), b[64:].contiguous())
 
     def _conv_split96(self, key: str, x: torch.Tensor, out: torch.Tensor, act: bool = True) -> None:
+        self._route(key, *x.shape, 96, 1, 1, act, False, forced="split96")
+        if self.planning:
+            return
         macs = x.shape[0] * 96 * x.shape[1] * 9 * x.shape[2] * x.shape[3]
         self.conv_macs["direct"] += macs
         self.conv_macs["executed"] += macs * 2 // 3 * 36 // 144 + macs // 3 * 16 // 36
@@ -345,44 +286,91 @@ class PwcPlan:
         ops.conv3x3_wino4(x, self.wino4_packed[key + "[:64]"], b0, 64, leaky_slope=slope, out=out[:, :64], workspace=self.workspace)
         ops.conv3x3_wino(x, self.wino_packed[key + "[64:]"], b1, 32, leaky_slope=slope, out=out[:, 64:], workspace=self.workspace)
 
+    # ---- which kernel runs a 3x3 layer: decided once per (layer, geometry) ------------------------
+    def _rule(self, n: int, cin: int, h: int, w: int, cout: int, stride: int, dilation: int, act: bool, has_residual: bool) -> str:
+        """Depends on the filter's shape, the geometry, the switches read when the plan was built and the library's measured rules;
+        never on which banks are packed."""
+        if self.conv_backend != "hip":
+            return "torch"                                         # BASELINE config[1]: convolutions by PyTorch-ROCm (MIOpen)
+        plain = stride == 1 and not has_residual
+        wino = self.wino and cout >= 32 and cin >= 16 and plain    # the layers the Winograd kernels are built for
+        if wino and self.wino4 and dilation == 1 and self._split96_wanted(n, cin, h, w, cout):
+            return "split96"
+        if self.pyr1_wino and (cout, cin) == (16, 16) and plain and dilation == 1 and act:
+            # first pyramid level: Winograd F(2x2,3x3) with the whole filter bank in LDS (125 instead of 180 us per layer at batch 16)
+            pyr1 = ops.pyr1_wino_preferred(n, h, w)
+            if pyr1:
+                return "pyr1x2" if pyr1 == 2 else "pyr1"           # x2: two consecutive such layers go as one launch (_conv16_pair)
+        if wino and self.wino4 and dilation == 1 and ops.conv3x3_wino4_preferred(n, cin, h, w, cout):
+            return "wino4"              # F(4x4,3x3): 4x fewer multiplications than the direct form, large well-filled layers (DESIGN.md 4b)
+        if wino and ops.conv3x3_wino_preferred(n, cin, h, w, cout, dilation):
+            return "wino2"              # F(2x2,3x3) on the matrix cores: 2.25x fewer MFMA passes for the same fp32 convolution
+        return "direct"
+
+    def _route(self, key: str, n: int, cin: int, h: int, w: int, cout: int, stride: int = 1, dilation: int = 1, act: bool = True,
+               has_residual: bool = False, forced: Optional[str] = None) -> str:
+        """"split96" | "pyr1" | "pyr1x2" | "wino4" | "wino2" | "direct" | "torch" for this launch, from the plan's table.  `forced`: the
+        site states its route (the lattice-major context network) instead of asking _rule.  A launch seen for the first time packs
+        the bank(s) its route reads; while the plan is built it also raises workspace_need to its kernel's demand.  After that the
+        table only grows for callers that drive _conv with shapes the plan does not launch (bench probes): they may pack, the
+        scratch stays -- every C entry compares the buffer with its own demand and runs unsplit when it is short."""
+        geo = (key, n, cin, h, w, cout, stride, dilation, act, has_residual, forced)
+        route = self.routes.get(geo)
+        if route is not None:
+            return route
+        route = self.routes[geo] = forced or self._rule(*geo[1:-1])
+        wt, need = self.p[key + ".weight"], 0
+        if route == "split96":
+            if key not in self.split96_bias:
+                self._pack_split96(key)
+            need = max(ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, 64), ops.conv3x3_wino_workspace_bytes(n, cin, h, w, 32, 1))
+        elif route in ("pyr1", "pyr1x2"):
+            if key not in self.pyr1_packed:
+                self.pyr1_packed[key] = ops.pack_pyr1_wino(wt)
+        elif route == "wino4":
+            if key not in self.wino4_packed:
+                self.wino4_packed[key] = ops.pack_conv3x3_wino4(wt)
+            need = ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, cout)
+        elif route == "wino2":
+            if key not in self.wino_packed:
+                self.wino_packed[key] = ops.pack_conv3x3_wino(wt)
+            need = ops.conv3x3_wino_workspace_bytes(n, cin, h, w, cout, dilation)
+        elif route == "direct":
+            if key not in self.packed:
+                self.packed[key] = ops.pack_conv3x3(wt)
+            need = ops.conv3x3_workspace_bytes(n, cin, h, w, cout, stride, dilation)
+        if self.planning:
+            self.workspace_need = max(self.workspace_need, need)
+        return route
+
     # ---- layer primitives -----------------------------------------------------------------------
     def _conv(self, name: str, x: torch.Tensor, out: torch.Tensor, stride: int = 1, dilation: int = 1,
-              act: bool = True, residual: Optional[torch.Tensor] = None) -> None:
+              act: bool = True, residual: Optional[torch.Tensor] = None, *, forced: Optional[str] = None, split2: bool = False) -> None:
+        """forced / split2 (the lattice-major context network): the route stated, not asked; F(4x4) storing its result as four pixel lattices"""
         key = name + ".0" if (name + ".0.weight") in self.p else name
         w, b = self.p[key + ".weight"], self.p[key + ".bias"]
-        if (key + "[:64]") in self.wino4_packed and stride == 1 and dilation == 1 and residual is None and self._split96_wanted(
-                x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[0]):
+        cout = w.shape[0]
+        route = self._route(key, *x.shape, cout, stride, dilation, act, residual is not None, forced)
+        if route == "split96":
             self._conv_split96(key, x, out, act)
             return
-        macs = x.shape[0] * w.shape[0] * w.shape[1] * 9 * ((x.shape[2] - 1) // stride + 1) * ((x.shape[3] - 1) // stride + 1)
+        if self.planning:
+            return
+        macs = x.shape[0] * cout * w.shape[1] * 9 * ((x.shape[2] - 1) // stride + 1) * ((x.shape[3] - 1) // stride + 1)
         self.conv_macs["direct"] += macs                          # what the layer costs as a direct convolution
-        if (key in self.pyr1_packed and stride == 1 and dilation == 1 and residual is None and act and x.dtype == torch.float32
-                and ops.pyr1_wino_preferred(x.shape[0], x.shape[2], x.shape[3])):
-            # first pyramid level: Winograd F(2x2,3x3) with the whole filter bank in LDS (125 instead of 180 us per layer at batch 16)
+        num, den = ROUTE_MACS[route]
+        self.conv_macs["executed"] += macs * num // den           # multiplications the matrix cores actually perform
+        slope = LEAKY if act else None
+        if route in ("pyr1", "pyr1x2"):
             ops.pyr1_wino(x, self.pyr1_packed[key], b, leaky_slope=LEAKY, out=out)
-            self.conv_macs["executed"] += macs * 16 // 36          # multiplications the matrix cores perform
-            return
-        if (self.wino and self.wino4 and key in self.wino_packed and self.conv_backend == "hip" and stride == 1 and dilation == 1 and residual is None
-                and x.dtype == torch.float32 and ops.conv3x3_wino4_preferred(x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[0])):
-            # Winograd F(4x4,3x3): 4x fewer multiplications than the direct form for the large, well-filled layers (gated: DESIGN.md 4b)
-            if key not in self.wino4_packed:
-                self.wino4_packed[key] = ops.pack_conv3x3_wino4(w)      # first (eager, warm-up) run; a captured replay finds it packed
-            ops.conv3x3_wino4(x, self.wino4_packed[key], b, w.shape[0], leaky_slope=LEAKY if act else None, out=out, workspace=self.workspace)
-            self.conv_macs["executed"] += macs * 36 // 144
-            return
-        if (self.wino and key in self.wino_packed and self.conv_backend == "hip" and stride == 1 and residual is None and x.dtype == torch.float32
-                and ops.conv3x3_wino_preferred(x.shape[0], x.shape[1], x.shape[2], x.shape[3], w.shape[0], dilation)):
-            # Winograd F(2x2,3x3) on the matrix cores: 2.25x fewer MFMA passes for the same fp32 convolution
-            ops.conv3x3_wino(x, self.wino_packed[key], b, w.shape[0], leaky_slope=LEAKY if act else None, out=out, dilation=dilation,
-                             workspace=self.workspace)
-            self.conv_macs["executed"] += macs * 16 // 36         # multiplications the matrix cores actually perform
-            return
-        self.conv_macs["executed"] += macs
-        if self.conv_backend == "hip":
-            ops.conv3x3(x, self.packed[key], b, w.shape[0], stride=stride, dilation=dilation,
-                        leaky_slope=LEAKY if act else None, residual=residual, out=out, workspace=self.workspace)
+        elif route == "wino4":
+            ops.conv3x3_wino4(x, self.wino4_packed[key], b, cout, leaky_slope=slope, out=out, split2=split2, workspace=self.workspace)
+        elif route == "wino2":
+            ops.conv3x3_wino(x, self.wino_packed[key], b, cout, leaky_slope=slope, out=out, dilation=dilation, workspace=self.workspace)
+        elif route == "direct":
+            ops.conv3x3(x, self.packed[key], b, cout, stride=stride, dilation=dilation, leaky_slope=slope, residual=residual, out=out,
+                        workspace=self.workspace)
         else:
-            # BASELINE config[1]: convolutions by PyTorch-ROCm (MIOpen); correlation/warp stay HIP.
             y = F.conv2d(x, w, b, stride=stride, padding=dilation, dilation=dilation)
             if act:
                 y = F.leaky_relu(y, LEAKY)
@@ -393,9 +381,11 @@ class PwcPlan:
     def _conv16_pair(self, name1: str, name2: str, x: torch.Tensor, out: torch.Tensor) -> bool:
         """Two consecutive 16 -> 16 layers (conv1aa, conv1b) as one launch where the rule says so; False: the caller runs them one by one"""
         k1, k2 = name1 + ".0", name2 + ".0"
-        if not (k1 in self.pyr1_packed and k2 in self.pyr1_packed and x.dtype == torch.float32
-                and ops.pyr1_wino_preferred(x.shape[0], x.shape[2], x.shape[3]) == 2):
+        geo = (*x.shape, self.p[k1 + ".weight"].shape[0])
+        if not (self._route(k1, *geo) == "pyr1x2" and self._route(k2, *geo) == "pyr1x2"):
             return False
+        if self.planning:
+            return True
         macs = 2 * x.shape[0] * 16 * 16 * 9 * x.shape[2] * x.shape[3]
         self.conv_macs["direct"] += macs
         self.conv_macs["executed"] += macs * 16 // 36              # the tiles' recomputed ring (1.22x on the first layer) is not counted
@@ -403,6 +393,8 @@ class PwcPlan:
         return True
 
     def _deconv(self, name: str, x: torch.Tensor, out: torch.Tensor) -> None:
+        if self.planning:
+            return
         w, b = self.p[name + ".weight"], self.p[name + ".bias"]
         if self.conv_backend == "hip":
             ops.deconv4x4s2(x, w, b, out=out)
@@ -443,10 +435,12 @@ class PwcPlan:
             self._conv(nb, bb, a)
             prev = a
 
-    def _decode(self) -> torch.Tensor:
+    def _decode(self) -> Optional[torch.Tensor]:
         """Coarse-to-fine decoder + context network over self.c1[l] / self.c2[l] (PWCNet.py:198-268)."""
         for l in (6, 5, 4, 3, 2):
             self._level_entry(l)
+            if l == 2 and not self.trunk2:
+                return None                                        # the caller (engine_strict) takes over from the level-2 base channels
             self._dense(l)
             self._heads(l)
         return self._context()
@@ -454,6 +448,8 @@ class PwcPlan:
     def _level_entry(self, l: int) -> None:
         """Cost volume of level l into its arena slot (PWCNet.py:198-199, 212-214 ...): plain correlation at level 6; below, c1
         into its slot and warp(c2, up_flow * scale) + correlation + LeakyReLU as one kernel."""
+        if self.planning:
+            return                                                 # no convolution, no scratch
         nd, base = self.nd, self.arena_base[l]
         ar = self.arena[l]
         c = PYRAMID_CH[l]
@@ -502,9 +498,14 @@ class PwcPlan:
         h, w = self.size[l]
         if l in self.head10:
             self._conv("head10_%d" % l, ar, self.head10[l], act=False)
-            ops.upsample_entry(self.head10[l], self.p["deconv%d.weight" % l], self.p["deconv%d.bias" % l], nxt[:, o:o + 4])
+            if not self.planning:
+                ops.upsample_entry(self.head10[l], self.p["deconv%d.weight" % l], self.p["deconv%d.bias" % l], nxt[:, o:o + 4])
             return
-        if self.stream_head[l]:
+        if self.stream_head[l] and self.planning:
+            # the one-pass kernel reads predict_flowL's direct bank and cuts a launch smaller than the chip along Cin through the scratch
+            self.packed["predict_flow%d" % l] = ops.pack_conv3x3(self.p["predict_flow%d.weight" % l])
+            self.workspace_need = max(self.workspace_need, ops.head_upfeat_workspace_bytes(*ar.shape))
+        elif self.stream_head[l]:
             # predict_flowL and upfeatL read the same 3x3 windows of the same arena: one pass
             ops.head_upfeat(ar, self.packed["predict_flow%d" % l], self.p["predict_flow%d.bias" % l],
                             self.p["upfeat%d.weight" % l], self.p["upfeat%d.bias" % l],
@@ -528,32 +529,21 @@ class PwcPlan:
     def _context_lattice(self) -> torch.Tensor:
         """The same seven layers with dc_conv1..5 in lattice-major layout (see __init__): every layer is the reference's layer on the
         same values, only the order in which pixels are stored between them differs."""
-        B = self.B
-
-        def w4(name, x, out, split2):
-            key = name + ".0"
-            w, b = self.p[key + ".weight"], self.p[key + ".bias"]
-            macs = x.shape[0] * w.shape[0] * w.shape[1] * 9 * x.shape[2] * x.shape[3]
-            self.conv_macs["direct"] += macs
-            self.conv_macs["executed"] += macs * 36 // 144
-            ops.conv3x3_wino4(x, self.wino4_packed[key], b, w.shape[0], leaky_slope=LEAKY, out=out, split2=split2, workspace=self.workspace)
-
-        w4("dc_conv1", self.arena[2], self.ctx[0], True)          # [B,565,H,W]      -> 4B  x [128,H/2,W/2]   (lattices of dilation 2)
-        w4("dc_conv2", self.ctx[0], self.ctx[1], True)            # dilation 2 = 1 on those -> 16B x [128,H/4,W/4]
-        w4("dc_conv3", self.ctx[1], self.ctx[2], True)            # dilation 4 = 1          -> 64B x [128,H/8,W/8]
+        w4 = dict(forced="wino4", split2=True)
+        self._conv("dc_conv1", self.arena[2], self.ctx[0], **w4)  # [B,565,H,W]      -> 4B  x [128,H/2,W/2]   (lattices of dilation 2)
+        self._conv("dc_conv2", self.ctx[0], self.ctx[1], **w4)    # dilation 2 = 1 on those -> 16B x [128,H/4,W/4]
+        self._conv("dc_conv3", self.ctx[1], self.ctx[2], **w4)    # dilation 4 = 1          -> 64B x [128,H/8,W/8]
         if self.ctx_lattice4:
-            w4("dc_conv4", self.ctx[2], self.ctx[3], True)        # dilation 8 = 1          -> 256B x [96,H/16,W/16]
-            w4("dc_conv5", self.ctx[3], self.ctx4_lat, False)     # dilation 16 = 1 on those (stacked tile groups: 7x16 images)
-            ops.lattice_unsplit(self.ctx4_lat, B, 4, out=self.ctx[4])
-            self._conv("dc_conv6", self.ctx[4], self.ctx[5], dilation=1)
-            self._conv("dc_conv7", self.ctx[5], self.flow_out, act=False, residual=self.flow[2])
-            return self.flow_out
-        if getattr(self, "dc4_split", False):                     # dilation 8 = 1 on the dilation-8 lattices: 64 couts F(4x4) + 32 couts F(2x2)
-            self._conv_split96("dc_conv4.0", self.ctx[2], self.ctx[3])
+            self._conv("dc_conv4", self.ctx[2], self.ctx[3], **w4)                 # dilation 8 = 1 -> 256B x [96,H/16,W/16]
+            self._conv("dc_conv5", self.ctx[3], self.ctx4_lat, forced="wino4")     # dilation 16 = 1 on those (stacked tile groups: 7x16 images)
         else:
-            self._conv("dc_conv4", self.ctx[2], self.ctx[3], dilation=1)
-        self._conv("dc_conv5", self.ctx[3], self.ctx4_lat, dilation=2)      # dilation 16 = 2 on them
-        ops.lattice_unsplit(self.ctx4_lat, B, 3, out=self.ctx[4])
+            if self.dc4_split:                                     # dilation 8 = 1 on the dilation-8 lattices: 64 couts F(4x4) + 32 couts F(2x2)
+                self._conv_split96("dc_conv4.0", self.ctx[2], self.ctx[3])
+            else:
+                self._conv("dc_conv4", self.ctx[2], self.ctx[3], dilation=1)
+            self._conv("dc_conv5", self.ctx[3], self.ctx4_lat, dilation=2)         # dilation 16 = 2 on them
+        if not self.planning:
+            ops.lattice_unsplit(self.ctx4_lat, self.B, 4 if self.ctx_lattice4 else 3, out=self.ctx[4])
         self._conv("dc_conv6", self.ctx[4], self.ctx[5], dilation=1)
         self._conv("dc_conv7", self.ctx[5], self.flow_out, act=False, residual=self.flow[2])
         return self.flow_out
@@ -570,7 +560,7 @@ class PwcPlan:
             for l in range(2, 6):
                 tot += (self.arena[l].numel() - self.pyr_a[l].numel()) * self.arena[l].element_size()
         tot += sum(t.numel() * t.element_size() for t in self.ctx + ([self.flow_out] if self.flow_out is not None else []))
-        if getattr(self, "ctx_lattice", False):
+        if self.ctx4_lat is not None:
             tot += self.ctx4_lat.numel() * self.ctx4_lat.element_size()
         tot += sum(t.numel() * t.element_size() for t in self.packed.values())
         tot += sum(t.numel() * t.element_size() for t in self.wino_packed.values())
@@ -581,33 +571,15 @@ class PwcPlan:
         return tot
 
 
-class PwcVideoPlan(PwcPlan):
-    """Plan for consecutive frame pairs (f[t], f[t+1]) of one video, the loop of
-    ``pwc_extract_flow_video.py:262-305`` (``frame1 = frame2`` each iteration).
-
-    The reference runs the feature pyramid on both frames of every pair, i.e. twice per frame.  Here each
-    level's pyramid buffer has B+1 batch slots: slot 0 carries the last frame of the previous step, slots
-    1..B receive the pyramid of the B new frames, and the decoder's first/second-image features are the
-    overlapping views [0:B] / [1:B+1] of the same buffer -- no copy, one pyramid pass per frame.
-    """
-
-    def __init__(self, params, B, H, W, device, dtype=torch.float32, md=4, normalize_corr=False,
-                 align_corners=False, conv_backend="hip", variant="dc"):
-        super().__init__(params, B, H, W, device, dtype, md, normalize_corr, align_corners, conv_backend, variant)
-        self.primed = False
-
-    @staticmethod
-    def _slots(B: int) -> int:
-        return B + 1
-
-    @staticmethod
-    def _pair_views(buf: torch.Tensor, B: int):
-        return buf[:B], buf[1:]
+class VideoDriver:
+    """prime() / push() of the video plans (PwcVideoPlan here, engine_f16.PwcVideoPlanF16): float32 frames in, B + 1 batch slots per
+    pyramid buffer, slot 0 carrying the last frame of the previous step.  The plan class provides _pyramid, _decode, pyr_a, B, H, W."""
+    primed = False
 
     def _check(self, frames: torch.Tensor, n: int) -> torch.Tensor:
-        if tuple(frames.shape) != (n, 3, self.H, self.W) or frames.dtype != self.dtype or frames.device != self.device:
-            raise ValueError("expected frames %s %s on %s, got %s %s on %s" % (
-                (n, 3, self.H, self.W), self.dtype, self.device, tuple(frames.shape), frames.dtype, frames.device))
+        if tuple(frames.shape) != (n, 3, self.H, self.W) or frames.dtype != torch.float32 or frames.device != self.device:
+            raise ValueError("expected float32 frames %s on %s, got %s %s on %s" % (
+                (n, 3, self.H, self.W), self.device, frames.dtype, tuple(frames.shape), frames.device))
         return ops.densify(frames)
 
     def _carry(self) -> None:
@@ -624,7 +596,7 @@ class PwcVideoPlan(PwcPlan):
     def push(self, frames: torch.Tensor) -> torch.Tensor:
         """B new frames [B,3,H,W] -> flows of the pairs (previous, frames[0]), (frames[0], frames[1]), ..."""
         if not self.primed:
-            raise RuntimeError("PwcVideoPlan.push before prime(first_frame)")
+            raise RuntimeError("%s.push before prime(first_frame)" % type(self).__name__)
         f = self._check(frames, self.B)
         self._pyramid([(f, 1, self.B + 1)], 1, self.B + 1)
         out = self._decode()
@@ -632,7 +604,33 @@ class PwcVideoPlan(PwcPlan):
         return out
 
     def run(self, x):
-        raise RuntimeError("PwcVideoPlan is driven by prime()/push(), not run()")
+        raise RuntimeError("%s is driven by prime()/push(), not run()" % type(self).__name__)
+
+
+class PwcVideoPlan(VideoDriver, PwcPlan):
+    """Plan for consecutive frame pairs (f[t], f[t+1]) of one video, the loop of
+    ``pwc_extract_flow_video.py:262-305`` (``frame1 = frame2`` each iteration).
+
+    The reference runs the feature pyramid on both frames of every pair, i.e. twice per frame.  Here each
+    level's pyramid buffer has B+1 batch slots: slot 0 carries the last frame of the previous step, slots
+    1..B receive the pyramid of the B new frames, and the decoder's first/second-image features are the
+    overlapping views [0:B] / [1:B+1] of the same buffer -- no copy, one pyramid pass per frame.
+    """
+
+    @staticmethod
+    def _slots(B: int) -> int:
+        return B + 1
+
+    @staticmethod
+    def _pair_views(buf: torch.Tensor, B: int):
+        return buf[:B], buf[1:]
+
+    def _plan_launches(self) -> None:
+        """what prime() and push() launch"""
+        B = self.B
+        self._pyramid([(self._images(1), B, B + 1)], B, B + 1)
+        self._pyramid([(self._images(B), 1, B + 1)], 1, B + 1)
+        self._decode()
 
 
 class PwcBidirPlan(PwcPlan):
@@ -665,15 +663,11 @@ class PwcBidirPlan(PwcPlan):
     def _pair_views(buf: torch.Tensor, B2: int):
         return buf[:B2], buf[B2 // 2:]
 
-    def _launch_geometries(self, B2: int, trunk2: bool):
-        # the pyramid runs on 2B = B2 images, not on all 3B slots: the shared scratch has to cover those launches too
-        out = super()._launch_geometries(B2, trunk2)
-        for l in range(1, 7):
-            h, w = self.size[l]
-            for n in self.pyramid_names[l - 1][1:]:
-                if n is not None:
-                    out.append((B2, PYRAMID_CH[l], h, w, PYRAMID_CH[l], 1))
-        return out
+    def _plan_launches(self) -> None:
+        """what run() launches: the pyramid on the 2B images (not on all 3B slots), the decoder at batch 2B"""
+        B = self.pairs
+        self._pyramid([(self._images(B), 0, B), (self._images(B), B, 2 * B)], 0, 2 * B)
+        self._decode()
 
     def run(self, img1: torch.Tensor, img2: torch.Tensor = None) -> Tuple[torch.Tensor, torch.Tensor]:
         B = self.pairs

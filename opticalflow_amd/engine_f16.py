@@ -31,8 +31,8 @@ import torch
 
 from . import _lib, ops
 from . import ops_f16 as F16
-from .engine import (CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PYRAMID_NAMES, PYRAMID_NAMES_OLD, WARP_SCALE, level_in_channels,
-                     old_variant_perm)
+from .engine import (CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PYRAMID_NAMES, PYRAMID_NAMES_OLD, WARP_SCALE, VideoDriver,
+                     level_in_channels, reorder_old_variant)
 
 DENSE_G = (40, 24, 12, 4, 0)          # group offset of conv{L}_i's output (conv_0 .. conv_4) inside the arena
 BASE_G = 56                           # first group after the dense-block outputs
@@ -65,15 +65,10 @@ def _phys_index(level: int, nd: int = 81) -> torch.Tensor:
 
 def prepare_params(params: Dict[str, torch.Tensor], variant: str, nd: int = 81) -> Dict[str, torch.Tensor]:
     """float32 copies of the parameters; PWCDCNet_old's filters re-ordered from its dense-block concatenation order to
-    PWCDCNet's (engine.old_variant_perm), as engine.PwcPlan does."""
+    PWCDCNet's (engine.reorder_old_variant), as engine.PwcPlan does."""
     p = {k: v.detach().float() for k, v in params.items()}
     if variant == "old":
-        for l in range(2, 7):
-            od = level_in_channels(l, nd)
-            keys = [("conv%d_%d.0.weight" % (l, k), k, 1) for k in range(1, 5)] + [("predict_flow%d.weight" % l, 5, 1)]
-            keys.append(("upfeat%d.weight" % l, 5, 0) if l > 2 else ("dc_conv1.0.weight", 5, 1))
-            for key, k, dim in keys:
-                p[key] = p[key].index_select(dim, old_variant_perm(k, od).to(p[key].device)).contiguous()
+        reorder_old_variant(p, nd)
     return p
 
 
@@ -293,14 +288,10 @@ class PwcPlanF16:
         return self.flow_out
 
 
-class PwcVideoPlanF16(PwcPlanF16):
+class PwcVideoPlanF16(VideoDriver, PwcPlanF16):
     """Half-precision plan for consecutive frame pairs of one video (pwc_extract_flow_video.py:262-305): B+1 batch
     slots per pyramid buffer, slot 0 carries the last frame of the previous step, the pair views overlap ([0:B] / [1:B+1]),
-    one pyramid pass per frame -- the fp16 twin of engine.PwcVideoPlan."""
-
-    def __init__(self, *args, **kwargs):
-        super().__init__(*args, **kwargs)
-        self.primed = False
+    one pyramid pass per frame -- the fp16 twin of engine.PwcVideoPlan, driven by the same prime() / push()."""
 
     @staticmethod
     def _slots(B: int) -> int:
@@ -308,31 +299,3 @@ class PwcVideoPlanF16(PwcPlanF16):
 
     def _pair_views(self, l: int):
         return self.pyr_a[l][:self.B], self.pyr_a[l][1:]
-
-    def _check(self, frames: torch.Tensor, n: int) -> torch.Tensor:
-        if tuple(frames.shape) != (n, 3, self.H, self.W) or frames.dtype != torch.float32 or frames.device != self.device:
-            raise ValueError("expected float32 frames %s on %s, got %s %s on %s" % (
-                (n, 3, self.H, self.W), self.device, frames.dtype, tuple(frames.shape), frames.device))
-        return ops.densify(frames)
-
-    def _carry(self) -> None:
-        for l in range(2, 7):
-            self.pyr_a[l][0].copy_(self.pyr_a[l][self.B])
-
-    def prime(self, frame: torch.Tensor) -> None:
-        f = self._check(frame, 1)
-        self._pyramid([(f, self.B, self.B + 1)], self.B, self.B + 1)
-        self._carry()
-        self.primed = True
-
-    def push(self, frames: torch.Tensor) -> torch.Tensor:
-        if not self.primed:
-            raise RuntimeError("PwcVideoPlanF16.push before prime(first_frame)")
-        f = self._check(frames, self.B)
-        self._pyramid([(f, 1, self.B + 1)], 1, self.B + 1)
-        out = self._decode()
-        self._carry()
-        return out
-
-    def run(self, x):
-        raise RuntimeError("PwcVideoPlanF16 is driven by prime()/push(), not run()")

@@ -136,11 +136,9 @@ class PwcPlanStrict:
         x = ops.densify(x)
         up.conv_macs = {"direct": 0, "executed": 0}
         up._pyramid([(x[:, :3], 0, B), (x[:, 3:], B, 2 * B)], 0, 2 * B)
-        for l in (6, 5, 4, 3):
-            up._level_entry(l)
-            up._dense(l)
-            up._heads(l)                      # level 3's heads write up_flow / up_feat into the fp32 level-2 base channels
-        up._level_entry(2)                    # c1 | fused warp + correlation + LeakyReLU, all fp32
+        # levels 6..3 (level 3's heads write up_flow / up_feat into the fp32 level-2 base channels) and the level-2 entry:
+        # c1 | fused warp + correlation + LeakyReLU, all fp32
+        up._decode()
         # hand-over: fp32 NCHW [corr 81 | c1 32 | up_flow 2 | up_feat 2] -> the c8 half arena's corr / c1 / flow groups + residuals
         base = up.arena[2]
         c = PYRAMID_CH[2]

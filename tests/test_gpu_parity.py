@@ -1398,42 +1398,115 @@ def test_conv3x3_winograd4_small_batch_whole_launch_split(gpu_device, case):
         assert all(torch.equal(r[:n], r[i * n:(i + 1) * n]) for i in range(1, B))
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("B", [1, 4])
-def test_plan_workspace_covers_every_launch(gpu_device, monkeypatch, B):
-    """the plan's shared scratch must cover the split-K / tail / whole-launch split of EVERY convolution it launches (the C side
-    falls back to the unsplit launch when the buffer is too small -- correct, and slow without anyone noticing).  Every conv call of one
-    forward is recorded and its workspace demand compared with what the plan holds; at these batch sizes the lattice-major context
-    network and the F(4x4) route with input-channel slices are in use."""
-    from opticalflow_amd import PWCDCNet, ops
+def _plan_net(gpu_device):
+    from opticalflow_amd import PWCDCNet
     from opticalflow_amd.weights import synthetic_state_dict
     net = PWCDCNet().to(gpu_device).eval()
     net.load_state_dict(synthetic_state_dict(net.manifest(), seed=0, gain=0.85, bias_std=0.02))
-    x = torch.rand(B, 6, 448, 1024, generator=torch.Generator().manual_seed(3)).to(gpu_device)
-    ref = net(x).clone()
-    plan = net._plan_for(x)
+    return net
+
+
+# (driver, batch / pairs, H, W): the benchmark size at two batches (lattice-major context network, F(4x4) with input-channel slices), then
+# the smallest shapes that reach each driver and each split route
+WORKSPACE_CASES = [("plan", 1, 448, 1024), ("plan", 4, 448, 1024),
+                   ("plan", 3, 128, 192),          # small maps, direct split-K
+                   ("plan", 5, 64, 64),            # head10, level 6 at 1x1
+                   ("video", 2, 128, 192),         # pyramid on 1 image (prime) and on B (push)
+                   ("bidir", 1, 128, 192)]         # pyramid on 2B of 3B slots, decoder at batch 2B
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", WORKSPACE_CASES, ids=["1", "4"] + ["%s-b%d-%dx%d" % c for c in WORKSPACE_CASES[2:]])
+def test_plan_workspace_covers_every_launch(gpu_device, monkeypatch, case):
+    """the plan's shared scratch must cover the split-K / tail / whole-launch split of EVERY convolution it launches and the
+    Cin slices of the streaming head (the C side falls back to the unsplit launch when the buffer is too small -- correct, and slow
+    without anyone noticing).  Every such call of one forward is recorded and its workspace demand compared with what the plan holds;
+    and the plan holds no more than that: workspace_need is the largest demand of a launch it makes, not of a route it declines."""
+    from opticalflow_amd import engine, ops
+    kind, B, H, W = case
+    net = _plan_net(gpu_device)
+    params = {k: v.detach() for k, v in net.state_dict().items()}
+    g = torch.Generator().manual_seed(3)
+    if kind == "plan":
+        x = torch.rand(B, 6, H, W, generator=g).to(gpu_device)
+        ref = net(x).clone()
+        plan = net._plan_for(x)
+
+        def drive():
+            return plan.run(x)
+    elif kind == "video":
+        frames = torch.rand(B + 1, 3, H, W, generator=g).to(gpu_device)
+        plan = engine.PwcVideoPlan(params, B, H, W, gpu_device)
+
+        def drive():
+            plan.prime(frames[:1])
+            return plan.push(frames[1:])
+        ref = drive().clone()
+    else:
+        img1, img2 = (torch.rand(B, 3, H, W, generator=g).to(gpu_device) for _ in range(2))
+        plan = engine.PwcBidirPlan(params, B, H, W, gpu_device)
+
+        def drive():
+            return torch.cat(plan.run(img1, img2))
+        ref = drive().clone()
     have = plan.workspace.numel() * 4 if plan.workspace is not None else 0
     calls = []
-    real = {n: getattr(ops, n) for n in ("conv3x3", "conv3x3_wino", "conv3x3_wino4")}
+    real = {n: getattr(ops, n) for n in ("conv3x3", "conv3x3_wino", "conv3x3_wino4", "head_upfeat")}
 
     def spy(name):
-        def f(xx, wp, bias, cout, *a, **kw):
+        def f(xx, wp, bias, *a, **kw):
             dil = kw.get("dilation", 1)
             n, cin, h, w = xx.shape
+            cout = 2 if name == "head_upfeat" else a[0]
             fn = {"conv3x3": lambda: ops.conv3x3_workspace_bytes(n, cin, h, w, cout, kw.get("stride", 1), dil),
                   "conv3x3_wino": lambda: ops.conv3x3_wino_workspace_bytes(n, cin, h, w, cout, dil),
-                  "conv3x3_wino4": lambda: ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, cout)}[name]
+                  "conv3x3_wino4": lambda: ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, cout),
+                  "head_upfeat": lambda: ops.head_upfeat_workspace_bytes(n, cin, h, w)}[name]
             calls.append((name, (n, cin, h, w, cout, dil), fn(), kw.get("workspace") is not None))
-            return real[name](xx, wp, bias, cout, *a, **kw)
+            return real[name](xx, wp, bias, *a, **kw)
         return f
     for n in real:
         monkeypatch.setattr(ops, n, spy(n))
-    out = plan.run(x) if hasattr(plan, "run") else net(x)
+    out = drive()
     assert torch.equal(out, ref)
-    assert len(calls) > 40 and any(c[0] == "conv3x3_wino4" for c in calls)
+    assert len(calls) > 40
     short = [c for c in calls if c[2] > have or (c[2] > 0 and not c[3])]
     assert not short, short
-    assert getattr(plan, "ctx_lattice", False), "lattice-major context network expected at batch %d" % B
+    print("%s: workspace_need %d B, %d launches, largest demand %d B" % (case, plan.workspace_need, len(calls), max(c[2] for c in calls)))
+    assert plan.workspace_need == have == max(c[2] for c in calls)
+    if (H, W) == (448, 1024):
+        assert any(c[0] == "conv3x3_wino4" for c in calls)
+        assert getattr(plan, "ctx_lattice", False), "lattice-major context network expected at batch %d" % B
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("B,H,W", [(3, 128, 192), (1, 448, 1024)])
+def test_plan_decides_at_build_time(gpu_device, monkeypatch, B, H, W):
+    """A plan resolves every convolution's route, packs that route's banks and sizes its scratch when it is built: eager forwards ask
+    the library's rules nothing, pack nothing, allocate nothing, and repeat bit for bit."""
+    from opticalflow_amd import ops
+    net = _plan_net(gpu_device)
+    x = torch.rand(B, 6, H, W, generator=torch.Generator().manual_seed(5)).to(gpu_device)
+    plan = net._plan_for(x)
+    banks = ("packed", "wino_packed", "wino4_packed", "pyr1_packed")
+
+    def snapshot():
+        torch.cuda.synchronize()
+        return {n: sorted(getattr(plan, n)) for n in banks}, dict(plan.routes), torch.cuda.memory_allocated()
+    before = snapshot()
+    assert before[1] and plan.workspace_need > 0
+    asked = {}
+    for n in ("conv3x3_wino4_preferred", "conv3x3_wino_preferred", "pyr1_wino_preferred"):
+        def counted(*a, _n=n, _real=getattr(ops, n), **kw):
+            asked[_n] = asked.get(_n, 0) + 1
+            return _real(*a, **kw)
+        monkeypatch.setattr(ops, n, counted)
+    first = plan.run(x).clone()
+    second = plan.run(x).clone()
+    assert not asked, asked
+    assert torch.equal(second, first)
+    del first, second
+    assert snapshot() == before
 
 
 @pytest.mark.gpu
