@@ -107,8 +107,11 @@ const char *pwc_last_error(void);
  *   images per workgroup, each with its own border -- serves them: 14x32 for a 32-cout launch, 7x16 for a 64-cout one; the fp32 plan then
  *   runs dc_conv4 / dc_conv5 on the level-4 lattices; 0: refused, the round-4 context path),
  *   "pyr1_wino" [PWC_PYR1_WINO] 1 (fp32 plans: the 16 -> 16 layers conv1aa / conv1b on pwc_pyr1_wino_fwd; 2: both as one
- *   pwc_pyr1_wino_pair_fwd launch -- measured slower, for A/B runs; 0: pwc_conv2d_fwd) and "pyr1_wino_min_tiles"
- *   [PWC_PYR1_WINO_MIN_TILES] 512 (8 x 64 tiles a launch needs for it: see pwc_pyr1_wino_preferred).
+ *   pwc_pyr1_wino_pair_fwd launch -- measured slower, for A/B runs; 0: pwc_conv2d_fwd), "pyr1_wino_min_tiles"
+ *   [PWC_PYR1_WINO_MIN_TILES] 512 (8 x 64 tiles a launch needs for it: see pwc_pyr1_wino_preferred) and
+ *   "w4_stagger" [PWC_W4_STAGGER] 1 (pwc_conv3x3_wino4_fwd: waves 4-7 of a workgroup place their patch reads and transforms behind other
+ *   MFMAs than waves 0-3, their partners on the SIMD -- the same bits; 1: in the forms and launch lengths where it measured faster,
+ *   2: in every launch, 0: one schedule for all waves).
  * Unknown name: PWC_EINVAL.  A captured HIP graph keeps the kernels chosen at capture time. */
 int pwc_set_option(const char *name, int value);
 int pwc_get_option(const char *name, int *value);

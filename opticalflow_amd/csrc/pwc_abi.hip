@@ -60,6 +60,8 @@ static constexpr OptDesc kOpts[OPT_COUNT] = {
                                                           // 0 = the direct MFMA kernel (read by the Python engine when a plan is built, and by pwc_pyr1_wino_preferred)
     {"pyr1_wino_min_tiles", "PWC_PYR1_WINO_MIN_TILES", 512},   // ... for launches of at least this many 8 x 64 tiles (two workgroups per CU; batch 1 at 448x1024 is 448 tiles and
                                                           // measured 0.2 % slower on the new kernel, so it keeps the direct one), pwc_pyr1_wino_preferred
+    {"w4_stagger", "PWC_W4_STAGGER", 1},                  // F(4x4) loop: waves 4-7 place their VALU bursts and LDS reads behind other MFMAs of a phase than waves 0-3, their
+                                                          // partners on the SIMD (bit-identical results): 1 = in the forms where it measured faster, 2 = in every form, 0 = parent schedule
 };
 // the table is indexed by enum Opt (pwc_common.h): a row out of order would silently give one switch another's value
 constexpr bool opt_is(Opt o, const char *name) {
@@ -74,7 +76,7 @@ static_assert(opt_is(OPT_CONV_WINO4, "conv_wino4") && opt_is(OPT_W4_TAILSPLIT, "
               opt_is(OPT_WARPCORR_WINDOW, "warpcorr_window") && opt_is(OPT_STREAM_SLICE_WGS, "stream_slice_wgs") &&
               opt_is(OPT_C1_IN_ARENA, "c1_in_arena") && opt_is(OPT_HEAD_SLICED_MIN_TILES, "head_sliced_min_tiles") &&
               opt_is(OPT_W4_STACKED, "w4_stacked") && opt_is(OPT_PYR1_WINO, "pyr1_wino") &&
-              opt_is(OPT_PYR1_WINO_MIN_TILES, "pyr1_wino_min_tiles"), "kOpts rows follow enum Opt");
+              opt_is(OPT_PYR1_WINO_MIN_TILES, "pyr1_wino_min_tiles") && opt_is(OPT_W4_STAGGER, "w4_stagger"), "kOpts rows follow enum Opt");
 static std::atomic<int> g_opt_val[OPT_COUNT];
 static std::atomic<unsigned char> g_opt_set[OPT_COUNT];
 

@@ -82,6 +82,10 @@ struct Geo4 {
     static constexpr int kRawWaves = kRawTail ? kRawTail / 64 : 8, kUWaves = kUTail ? kUTail / 64 : 8;   // waves that issue the last instruction
     static_assert(kSmemBytes <= 160 * 1024, "LDS");
     static_assert(kThreads % kCoutT == 0, "one U offset register: instruction j is j * (kThreads / kCoutT) rows further");
+    // does the staggered schedule of waves 4-7 (wino4p_body, SH = 1) run by default?  Per form, as measured (profiles/r10_wino4_stagger_notes.md):
+    // yes for the 64-column groups (x1.02-1.04 on the long layers of levels 2 and 3) and the 7x16 stack (dc_conv5 x1.02); the
+    // 32-column forms measured x0.94-0.98 (plain, level 5's short sliced launches) and x1.00 (14x32 stack)
+    static constexpr bool kStagger = GW == 64 || (GW == 16 && IH > 0);
 };
 
 // Interpolation points 0, +-a, +-b, inf with a = 3/4, b = 3/2 instead of the textbook 0, +-1, +-2: the same operation count, every
@@ -199,7 +203,20 @@ __device__ __forceinline__ void bt3_row(const float (&d)[6], float (&t)[3]) {   
     asm volatile("" : "+v"(t[0]), "+v"(t[1]), "+v"(t[2]));
 }
 
-template <int CB, int TG, int GW, int IH, int HJ>
+// STAGGER (SH = 1, waves 4-7 only; option "w4_stagger"): the two waves that share a SIMD are waves w and w + 4 -- the same position half,
+// the same cout group, another tile group -- so they run the SAME instruction stream, re-aligned by the barrier of every chunk: both
+// reach their VALU bursts and their LDS reads behind the same MFMAs, and while both are in a burst nobody feeds the matrix pipe.  The
+// second half of the workgroup therefore places the same work behind OTHER MFMAs of the phase (kMP, kMV, kMR in the body), so that one
+// wave's burst lies beside its partner's run of MFMAs.  Nothing moves out of its phase and no value changes: the hazards, the counted
+// waits and the results (bit for bit) are the parent's.  What pays is moving the patch-row reads two or more MFMAs away from the
+// partner's (and from the first LDS-DMA piece); the VALU shift adds about a third.  Measurements and the placements that lost:
+// profiles/r10_wino4_stagger_notes.md.
+#ifndef PWC_W4_STAG_P
+#define PWC_W4_STAG_P 2       // patch-row reads               (first half: 0)
+#define PWC_W4_STAG_V 6       // V-column transform, 12 VALU   (4)
+#define PWC_W4_STAG_R 10      // two row transforms, 12 VALU   (8)
+#endif                        // the U reads (behind MFMAs 6 and 10) and the LDS-DMA pieces stay where they are: moving them measured slower
+template <int CB, int TG, int GW, int IH, int HJ, int SH>
 __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
                                             float *__restrict__ y, int B, int Cin_all, int H, int W, int Cout, int CoutP, int tiles_x, int tiles_y,
                                             int64_t bsx, int64_t bsy, float slope, int do_leaky, int co0, int nblk, int ngroups, int split2,
@@ -376,6 +393,9 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
 #define PWC_W4_DMASTRIDE 4
 #endif
     constexpr int kDmaStride = PWC_W4_DMASTRIDE;
+    // MFMA index of a phase behind which this wave puts each piece of the phase's other work
+    constexpr int kMP = SH ? PWC_W4_STAG_P : 0, kMV = SH ? PWC_W4_STAG_V : 4, kMR = SH ? PWC_W4_STAG_R : 8;
+    static_assert(kMP >= 0 && kMP < kMR && kMR < 12 && kMV >= 0 && kMV < 12, "the patch rows are read before their transform, all inside the phase");
     static_assert((G::kRS + G::kUS - 1) * kDmaStride + 1 < 36, "the pieces of a group fit one iteration");
     auto iteration = [&](int k, float (&wc)[6][3], float (&wn)[6][3], auto par_tag) {
         constexpr int PAR = decltype(par_tag)::value;
@@ -403,18 +423,18 @@ __device__ __forceinline__ void wino4p_body(const float *__restrict__ x, const f
                 if (use_v1) PWC_W4P_MFMA(cbl, 6 * jj + i, ucur[cbl][(p >> 2) - gb][p & 3], v1[i]);
                 else        PWC_W4P_MFMA(cbl, 6 * jj + i, ucur[cbl][(p >> 2) - gb][p & 3], v0[i]);
                 // ---- in the shadow of this MFMA ----------------------------------------------------------------------
-                if (m == 0 && !(PWC_W4_EXP & 32)) { load_row(rnext, 2 * ph, da); load_row(rnext, 2 * ph + 1, db); }
+                if (m == kMP && !(PWC_W4_EXP & 32)) { load_row(rnext, 2 * ph, da); load_row(rnext, 2 * ph + 1, db); }
                 if (!(PWC_W4_EXP & 4)) {                        // LDS-DMA of {raw(k+3), U(k+2)}: ONE piece per kDmaStride MFMAs
                     if (ph == 0 && m == 0) setup_dma(k);
                     const int t = 12 * ph + m - 1;
                     if (t >= 0 && t % kDmaStride == 0 && t / kDmaStride < G::kRS + G::kUS) dma_piece(t / kDmaStride);
                 }
-                if (m == 4) {                                   // V column ph of THIS chunk (consumed by the next phase) + two row transforms
+                if (m == kMV) {                                 // V column ph of THIS chunk (consumed by the next phase) + two row transforms
                     const float col[6] = {wc[0][ph], wc[1][ph], wc[2][ph], wc[3][ph], wc[4][ph], wc[5][ph]};
                     const bool dst_v1 = (PAR + ph) & 1;
                     if (dst_v1) { bt6(col, v1); pin6(v1); } else { bt6(col, v0); pin6(v0); }
                 }
-                if (m == 8) { bt3_row<HJ>(da, wn[2 * ph]); bt3_row<HJ>(db, wn[2 * ph + 1]); }
+                if (m == kMR) { bt3_row<HJ>(da, wn[2 * ph]); bt3_row<HJ>(db, wn[2 * ph + 1]); }
                 // U groups of column ph of this chunk, multiplied by the next phase (phase 2's: by the next iteration's phase 0)
                 if (m == 6 || m == 10) {
                     const int cb_ = m == 6 ? 0 : 1;
@@ -545,12 +565,19 @@ template <int CB, int TG, int GW, int IH>
 __global__ void __launch_bounds__(kThreads, 1)
 conv3x3_wino4p_kernel(const float *__restrict__ x, const float *__restrict__ up, const float *__restrict__ bias,
                       float *__restrict__ y, int B, int Cin, int H, int W, int Cout, int CoutP, int tiles_x, int tiles_y,
-                      int64_t bsx, int64_t bsy, float slope, int do_leaky, int co0, int nblk, int ngroups, int split2, const TailSplit ts) {
-    // the position half is wave-uniform: two specialisations of the body, every index inside is a compile-time constant
-    if (__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) & 1)
-        wino4p_body<CB, TG, GW, IH, 1>(x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, nblk, ngroups, split2, ts);
-    else
-        wino4p_body<CB, TG, GW, IH, 0>(x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, nblk, ngroups, split2, ts);
+                      int64_t bsx, int64_t bsy, float slope, int do_leaky, int co0, int nblk, int ngroups, int split2, int stagger,
+                      const TailSplit ts) {
+    // the position half and the schedule (staggered: the second half of the workgroup) are wave-uniform: four specialisations of the
+    // body, every index inside is a compile-time constant
+#define PWC_W4P_BODY(HJ_, SH_) \
+    wino4p_body<CB, TG, GW, IH, HJ_, SH_>(x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, nblk, ngroups, split2, ts)
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    if (stagger && wave >= 4) {
+        if (wave & 1) PWC_W4P_BODY(1, 1); else PWC_W4P_BODY(0, 1);
+    } else {
+        if (wave & 1) PWC_W4P_BODY(1, 0); else PWC_W4P_BODY(0, 0);
+    }
+#undef PWC_W4P_BODY
 }
 
 // Finishes the tiles of a tail launch: y = act(bias + sum over slices, in slice order (deterministic)) for couts co0 .. co0 + ncout - 1
@@ -686,6 +713,10 @@ inline TailPlan wino4_tail_plan(int B, int64_t nblk, int ngroups, int nchunks, i
     return p;
 }
 
+// The staggered schedule pays in the K loop and costs at its ends (four specialisations of the unrolled body instead of two are
+// fetched): x1.02-1.04 from 24 chunks per workgroup up, x1.00 at 16, x0.96-0.98 at the 8-11 chunks of a slice of a small launch
+constexpr int kStaggerMinChunks = 16;
+
 template <int CB, int TG, int GW, int IH = 0>
 int launch_wino4(const float *x, const float *up, const float *bias, float *y, int B, int Cin, int H, int W, int Cout,
                  int64_t bsx, int64_t bsy, float slope, int do_leaky, hipStream_t st, int co0, int ngroups, int split2,
@@ -699,6 +730,10 @@ int launch_wino4(const float *x, const float *up, const float *bias, float *y, i
         PWC_FAIL(PWC_EUNSUPPORTED, "pwc_conv3x3_wino4_fwd: stacked tile groups need H <= %d, W <= %d, Cin %% 4 == 0 and 31-bit offsets", IH, GW);
     const int CoutP = cout_padded4(Cout);
     constexpr int kTH = G::kTH;
+    // option "w4_stagger": 0 = every wave on the parent schedule, 1 = waves 4-7 staggered in the forms where that measured faster
+    // (Geo4::kStagger) and for workgroups of at least kStaggerMinChunks chunks, 2 = in every launch (measurements)
+    const int sopt = pwc::option(pwc::OPT_W4_STAGGER);
+    auto stagger_for = [&](int chunks) { return (sopt >= 2 || (sopt == 1 && G::kStagger && chunks >= kStaggerMinChunks)) ? 1 : 0; };
     // stacked: the tile arithmetic (tail split, XCD order) runs over groups of kImg images, as the plain form runs over images
     const int Bg = (B + G::kImg - 1) / G::kImg;
     const int tiles_x = (W + GW - 1) / GW, tiles_y = IH ? 1 : (H + kTH - 1) / kTH;
@@ -709,12 +744,13 @@ int launch_wino4(const float *x, const float *up, const float *bias, float *y, i
     if (tp.main_tiles > 0)
         hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(tp.main_tiles * ngroups)), dim3(kThreads), kSmemP, st,
                            x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, tp.main_tiles, ngroups, split2,
+                           stagger_for((Cin + kCK - 1) / kCK),
                            TailSplit{tp.main_tiles / Bg, 0, 1, 0, nullptr});
     if (tp.ksplit > 1) {
         const int ntail = (int)nblk - tp.main_tiles;
         float *ws = static_cast<float *>(workspace);
         hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(ntail * ngroups * tp.ksplit)), dim3(kThreads), kSmemP, st,
-                           x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, ntail, ngroups, 0,
+                           x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, ntail, ngroups, 0, stagger_for(tp.cps),
                            TailSplit{ntail / Bg, tp.main_tiles / Bg, tp.ksplit, tp.cps, ws});
         const int ncout = min(ngroups * G::kCoutT, Cout - co0);
         const int64_t total = (int64_t)ntail * ncout * kTH * (GW / 4);

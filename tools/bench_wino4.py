@@ -1,6 +1,9 @@
 #!/usr/bin/env python3
 """Winograd F(4x4,3x3) (pwc_conv3x3_wino4_fwd) against F(2x2,3x3): max / rms error vs an fp64 reference on small and ragged cases,
-then the forward's large layers at batch 16 (HIP-event means).  usage: bench_wino4.py [check|layers|all]"""
+then the forward's large layers at batch 16 (HIP-event means).  usage: bench_wino4.py [check|layers|all|pmc]
+bench_wino4.py layers <option> <a> <b>: the F(4x4) layers under two values of a pwc_set_option switch, alternating in one process
+(five rounds each; median, and the min-max spread of the rounds).  bench_wino4.py forms <option> <a> <b>: the same for launches of the
+other Geo4 forms (32-column groups, stacked images): level 5 and the context network's lattice layers of a batch-16 forward."""
 import os
 import sys
 
@@ -67,7 +70,9 @@ def t(fn, reps=10):
     return s.elapsed_time(e) / reps
 
 
-if mode in ("layers", "all"):
+AB = (sys.argv[2], int(sys.argv[3]), int(sys.argv[4])) if mode in ("layers", "forms") and len(sys.argv) > 4 else None
+
+if mode in ("layers", "all", "forms"):
     B = int(os.environ.get("PWC_BENCH_BATCH", "16"))
     LAYERS = [("conv2aa/b", 2 * B, 32, 32, 112, 256), ("conv3aa/b", 2 * B, 64, 64, 56, 128),
               ("conv3_0", B, 149, 128, 56, 128), ("conv3_1", B, 277, 128, 56, 128), ("conv3_2", B, 405, 96, 56, 128),
@@ -75,6 +80,9 @@ if mode in ("layers", "all"):
               ("conv2_0", B, 117, 128, 112, 256), ("conv2_1", B, 245, 128, 112, 256), ("conv2_2", B, 373, 96, 112, 256),
               ("conv2_3", B, 469, 64, 112, 256), ("conv2_4", B, 533, 32, 112, 256), ("dc_conv1", B, 565, 128, 112, 256),
               ("dc_conv6", B, 64, 32, 112, 256)]
+    if mode == "forms":         # <4,2,32>; <4,2,32> + <2,4,32,16>; <2,4,32,16>; <4,2,16,8>; <2,4,32> (no layer of the forward: a made-up one)
+        LAYERS = [("conv5a/b", 2 * B, 128, 128, 14, 32), ("conv5_1", B, 341, 128, 14, 32), ("dc_conv4", 64 * B, 128, 96, 14, 32),
+                  ("dc_conv4/32", 64 * B, 128, 32, 14, 32), ("dc_conv5", 256 * B, 96, 64, 7, 16), ("<2,4,32>", 4 * B, 128, 32, 32, 32)]
     tot = [0.0, 0.0]
     for name, b, cin, cout, H, W in LAYERS:
         x = torch.randn(b, cin, H, W, device=dev)
@@ -82,6 +90,24 @@ if mode in ("layers", "all"):
         bias = torch.randn(cout, device=dev) * 0.1
         u2, u4 = ops.pack_conv3x3_wino(w), ops.pack_conv3x3_wino4(w)
         y2, y4 = torch.empty(b, cout, H, W, device=dev), torch.empty(b, cout, H, W, device=dev)
+        if AB:
+            if mode == "layers" and not ops.conv3x3_wino4_preferred(b, cin, H, W, cout):
+                continue
+            ws = torch.empty(max(1, ops.conv3x3_wino4_workspace_bytes(b, cin, H, W, cout) // 4), device=dev)       # as the plan runs it
+            opt, res, outs = AB[0], {AB[1]: [], AB[2]: []}, {}
+            for r in range(5):
+                for v in AB[1:]:
+                    _lib.set_option(opt, v)
+                    res[v].append(t(lambda: ops.conv3x3_wino4(x, u4, bias, cout, out=y4, workspace=ws)) * 1e3)
+                    outs[v] = y4.clone()
+            kern = _lib.load().pwc_last_conv_kernel().decode()
+            ra, rb = sorted(res[AB[1]]), sorted(res[AB[2]])
+            print("%-10s %3d->%3d @%3dx%-3d: %s=%d %7.1f us (%.1f-%.1f)   %s=%d %7.1f us (%.1f-%.1f)   x%.3f   equal=%s   %s"
+                  % (name, cin, cout, H, W, opt, AB[1], ra[2], ra[0], ra[4], opt, AB[2], rb[2], rb[0], rb[4], ra[2] / rb[2],
+                     torch.equal(outs[AB[1]], outs[AB[2]]), kern), flush=True)
+            tot[0] += ra[2]
+            tot[1] += rb[2]
+            continue
         t2 = t(lambda: ops.conv3x3_wino(x, u2, bias, cout, out=y2))
         t4 = t(lambda: ops.conv3x3_wino4(x, u4, bias, cout, out=y4))
         kern = _lib.load().pwc_last_conv_kernel().decode()
@@ -91,4 +117,7 @@ if mode in ("layers", "all"):
         print("%-10s %3d->%3d @%3dx%-3d: F(2x2) %7.1f us   F(4x4) %7.1f us (%.2f of the fp32 MFMA peak)   x%.2f   preferred=%d   max diff %.1e   %s"
               % (name, cin, cout, H, W, t2 * 1e3, t4 * 1e3, gf4 / t4 / 157.3, t2 / t4, ops.conv3x3_wino4_preferred(b, cin, H, W, cout),
                  (y2 - y4).abs().max().item(), kern), flush=True)
-    print("sum: F(2x2) %.1f us, F(4x4) %.1f us" % (tot[0] * 1e3, tot[1] * 1e3))
+    if AB:
+        print("sum of medians: %s=%d %.1f us, %s=%d %.1f us" % (AB[0], AB[1], tot[0], AB[0], AB[2], tot[1]))
+    else:
+        print("sum: F(2x2) %.1f us, F(4x4) %.1f us" % (tot[0] * 1e3, tot[1] * 1e3))
