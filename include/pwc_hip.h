@@ -458,6 +458,41 @@ int pwc_kitti_ingest_u8(const void *pairs_u8, void *x, int n, int H, int W, cons
 int pwc_flow_upsample_f32(const void *flow_q, void *out, int n, int Hq, int Wq, int crop_h, int crop_w, int out_h, int out_w,
                           int64_t q_bstride, void *stream);
 
+/* KITTI scoring on the device (ABI v13 additions, csrc/pwc_kitti_score.hip): EPE and Fl-all of inference_kitti.py:94-128
+ * (epe_metric / fl_all_metric) straight from the network's quarter-resolution flow, nothing image-sized written unless asked for.
+ * flow_q [n][2][Hq][Wq] f32 (dense planes, batch stride in elements).  Per pixel (b, y, x) of the out_h x out_w grid, in fp32 with
+ * no fused multiply-add:
+ *   1. pred = what pwc_flow_upsample_f32(flow_q, crop_h, crop_w, out_h, out_w) writes at that pixel -- the same crop, rh / rw / su /
+ *        sv and expression order (one shared device function, csrc/pwc_flow_up.h); with (crop_h, crop_w) == (out_h, out_w) every
+ *        interpolation weight is exactly 1 or 0 and the scale is 1, so the value is the field's own;
+ *   2. ground truth, gt_kind 0: gt = float planes [n][2][out_h][out_w], valid = uint8 [n][out_h][out_w] (non-zero = valid) or NULL
+ *        (every pixel valid);  gt_kind 1: gt = the KITTI PNG samples themselves, uint16 [n][out_h][out_w][3] in R, G, B order:
+ *        u = ((float)R - 32768.f) / 64.f, v alike from G, valid = (B != 0) (load_flow_kitti_png, inference_kitti.py:23-52); valid
+ *        must be NULL;
+ *   3. du = pred.u - gt.u;  dv alike;  epe = sqrtf(du*du + dv*dv);  mag = sqrtf(gu*gu + gv*gv);
+ *        the pixel is an OUTLIER when epe > fmaxf(3.0f, 0.05f * mag)  (inference.py:129-159 compute_fl writes the same predicate as
+ *        (epe > 3) & (epe > 0.05 * mag));
+ *   4. per sample b: {fp64 sum of epe over valid pixels (each fp32 epe added in fp64), int64 #valid, int64 #valid outliers}.
+ * out (device, float [n][2]): out[b] = {(float)(sum / #valid), (float)(100.0 * #outliers / #valid)}; both NaN when #valid == 0
+ * (the reference's np.nan; inference.py returns 0.0 there -- a caller who wants that reads the raw counts).  Each 16 x 64 tile leaves
+ * its three totals in the workspace, summed in a fixed tree order, and one final workgroup per sample adds that sample's tiles in
+ * order: no atomics, bit-reproducible, no host synchronisation.
+ * flow_out: NULL, or float [n][2][out_h][out_w] (dense) that also receives the full-resolution flow, bit-identical to
+ * pwc_flow_upsample_f32.
+ * workspace: device, 8-byte aligned, pwc_kitti_score_workspace_bytes(n, out_h, out_w) = 24 * n * (1 + tiles per sample) bytes (-1
+ * for a non-positive size).  After the launch its first 24 n bytes hold the raw totals, [n][3] 8-byte words: fp64 sum, int64 #valid,
+ * int64 #outliers.
+ * PWC_EINVAL, nothing launched: null flow_q / gt / workspace / out, non-positive sizes, crop_h > Hq or crop_w > Wq, q_bstride <
+ * 2*Hq*Wq, gt_kind not 0 or 1, valid != NULL with gt_kind 1, n*2*out_h*out_w >= 2^31, n > 65535, out_h > 16 * 65535, a workspace
+ * that is too small.  PWC_EALIGN, nothing launched: a workspace not 8-byte aligned, flow_q / flow_out / out / float gt not 4-byte
+ * aligned, uint16 gt not 2-byte aligned. */
+int64_t pwc_kitti_score_workspace_bytes(int n, int out_h, int out_w);
+int pwc_kitti_score(const void *flow_q, int n, int Hq, int Wq, int crop_h, int crop_w, int out_h, int out_w,
+                    int64_t q_bstride,
+                    const void *gt, int gt_kind, const void *valid,
+                    void *flow_out /* may be NULL */, void *workspace, int64_t workspace_bytes,
+                    void *out /* float [n][2] */, void *stream);
+
 /* ---- fp16 convolution (first piece of the half-precision path, BASELINE configs 3-4) --------------------------
  * Activations are channel-blocked "c8": [B][ceil(C/8)][H][W][8] halves, channels past C zero; only the batch
  * stride (in halves, multiple of 8) is free, so a tensor may be a channel-group slice of an arena.  fp32

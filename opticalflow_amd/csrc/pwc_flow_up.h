@@ -24,4 +24,42 @@ __device__ __forceinline__ float2 up_flow(const float *f, const G &g, int Y, int
     return make_float2(u * g.sx, v * g.sy);
 }
 
+// Cropped upsample of the KITTI evaluation loop (`unpad` + `flow_resize` of inference_kitti.py:66-91), shared by flow_upsample_kernel
+// (pwc_kitti.hip) and the score kernel (pwc_kitti_score.hip) so that both evaluate it with the same fp32 operations in the same order:
+// the top-left hc x wc of a [2][Hq][Wq] field, bilinear with align_corners = True (F.interpolate's arithmetic: source = dst * (in - 1) /
+// (out - 1), weights 1 - l and l), u * (w / wc), v * (h / hc).
+struct CropUp {
+    int Hq, Wq, hc, wc;
+    float rh, rw, su, sv;
+};
+
+inline CropUp crop_up_make(int Hq, int Wq, int crop_h, int crop_w, int out_h, int out_w) {
+    CropUp g;
+    g.Hq = Hq; g.Wq = Wq; g.hc = crop_h; g.wc = crop_w;
+    // F.interpolate(align_corners = True): scale = (in - 1) / (out - 1) in float (0 for a one-pixel output)
+    g.rh = out_h > 1 ? (float)(crop_h - 1) / (float)(out_h - 1) : 0.f;
+    g.rw = out_w > 1 ? (float)(crop_w - 1) / (float)(out_w - 1) : 0.f;
+    g.su = (float)((double)out_w / (double)crop_w);
+    g.sv = (float)((double)out_h / (double)crop_h);
+    return g;
+}
+
+// (u, v) at output pixel (y, x); p = quarter-resolution flow of this item ([2][Hq][Wq])
+__device__ __forceinline__ float2 crop_up_flow(const float *__restrict__ p, const CropUp &g, int y, int x) {
+    const float fy = g.rh * (float)y, fx = g.rw * (float)x;
+    const int y0 = (int)fy, x0 = (int)fx;
+    const int y1 = y0 + (y0 < g.hc - 1 ? 1 : 0), x1 = x0 + (x0 < g.wc - 1 ? 1 : 0);
+    const float ly = fy - (float)y0, lx = fx - (float)x0, my = 1.0f - ly, mx = 1.0f - lx;
+    const int64_t plane = (int64_t)g.Hq * g.Wq;
+    float r[2];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        const float *pc = p + c * plane;
+        const float v = my * (mx * pc[(int64_t)y0 * g.Wq + x0] + lx * pc[(int64_t)y0 * g.Wq + x1]) +
+                        ly * (mx * pc[(int64_t)y1 * g.Wq + x0] + lx * pc[(int64_t)y1 * g.Wq + x1]);
+        r[c] = v * (c == 0 ? g.su : g.sv);
+    }
+    return make_float2(r[0], r[1]);
+}
+
 }  // namespace pwc

@@ -13,6 +13,7 @@
 #include <stdint.h>
 
 #include "pwc_common.h"
+#include "pwc_flow_up.h"
 
 namespace {
 
@@ -49,29 +50,18 @@ kitti_ingest_kernel(const uint8_t *__restrict__ src, float *__restrict__ dst, in
         *reinterpret_cast<f32x4 *>(o + (int64_t)c * Hp * Wp) = (f32x4){v[c][0], v[c][1], v[c][2], v[c][3]};
 }
 
-// thread = one output pixel, both channels
+// thread = one output pixel, both channels (the arithmetic is pwc_flow_up.h's crop_up_flow, shared with the score kernel)
 __global__ void __launch_bounds__(256)
-flow_upsample_kernel(const float *__restrict__ q, float *__restrict__ out, int Hq, int Wq, int hc, int wc, int h, int w, int64_t bsq,
-                     float rh, float rw, float su, float sv, int64_t total) {
+flow_upsample_kernel(const float *__restrict__ q, float *__restrict__ out, pwc::CropUp g, int h, int w, int64_t bsq, int64_t total) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= total) return;
     const int x = (int)(idx % w);
     int64_t t = idx / w;
     const int y = (int)(t % h);
     const int64_t b = t / h;
-    const float fy = rh * (float)y, fx = rw * (float)x;
-    const int y0 = (int)fy, x0 = (int)fx;
-    const int y1 = y0 + (y0 < hc - 1 ? 1 : 0), x1 = x0 + (x0 < wc - 1 ? 1 : 0);
-    const float ly = fy - (float)y0, lx = fx - (float)x0, my = 1.0f - ly, mx = 1.0f - lx;
-    const float *p = q + b * bsq;
-    const int64_t plane = (int64_t)Hq * Wq;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const float *pc = p + c * plane;
-        const float v = my * (mx * pc[(int64_t)y0 * Wq + x0] + lx * pc[(int64_t)y0 * Wq + x1]) +
-                        ly * (mx * pc[(int64_t)y1 * Wq + x0] + lx * pc[(int64_t)y1 * Wq + x1]);
-        out[((b * 2 + c) * h + y) * (int64_t)w + x] = v * (c == 0 ? su : sv);
-    }
+    const float2 v = pwc::crop_up_flow(q + b * bsq, g, y, x);
+    out[((b * 2 + 0) * h + y) * (int64_t)w + x] = v.x;
+    out[((b * 2 + 1) * h + y) * (int64_t)w + x] = v.y;
 }
 
 }  // namespace
@@ -102,14 +92,10 @@ extern "C" int pwc_flow_upsample_f32(const void *flow_q, void *out, int n, int H
     if (n <= 0 || Hq <= 0 || Wq <= 0 || crop_h <= 0 || crop_w <= 0 || crop_h > Hq || crop_w > Wq || out_h <= 0 || out_w <= 0)
         PWC_FAIL(PWC_EINVAL, "pwc_flow_upsample_f32: bad shape");
     if (q_bstride < (int64_t)2 * Hq * Wq) PWC_FAIL(PWC_EINVAL, "pwc_flow_upsample_f32: batch stride smaller than the tensor");
-    // F.interpolate(align_corners = True): scale = (in - 1) / (out - 1) in float (0 for a one-pixel output)
-    const float rh = out_h > 1 ? (float)(crop_h - 1) / (float)(out_h - 1) : 0.f;
-    const float rw = out_w > 1 ? (float)(crop_w - 1) / (float)(out_w - 1) : 0.f;
-    const float su = (float)((double)out_w / (double)crop_w), sv = (float)((double)out_h / (double)crop_h);
+    const pwc::CropUp g = pwc::crop_up_make(Hq, Wq, crop_h, crop_w, out_h, out_w);
     const int64_t total = (int64_t)n * out_h * out_w;
     if ((total + 255) / 256 > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_flow_upsample_f32: grid too large");
     hipLaunchKernelGGL(flow_upsample_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
-                       static_cast<const float *>(flow_q), static_cast<float *>(out), Hq, Wq, crop_h, crop_w, out_h, out_w, q_bstride,
-                       rh, rw, su, sv, total);
+                       static_cast<const float *>(flow_q), static_cast<float *>(out), g, out_h, out_w, q_bstride, total);
     return pwc::check_launch("flow_upsample_kernel");
 }

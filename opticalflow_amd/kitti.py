@@ -13,6 +13,10 @@ being stretched to 1242x375.  `model_infer(..., reference_unpad=False)` crops by
 `PairStream` is the config-5 ingest: uint8 pairs are staged in pinned host buffers and uploaded on a side
 stream while the previous pair is being processed (double buffering); normalisation happens on the device
 (2.8 MB/pair over PCIe instead of 11.2 MB as fp32).
+
+`evaluate_stream` / `ScoredInfer` score on the device as well: the captured pipeline ends in the fused EPE / Fl-all kernel
+(csrc/pwc_kitti_score.hip) instead of the upsample kernel, the ground truth travels with the images, and one [N,3] table of
+raw totals is downloaded at the end.  `evaluate_pairs` is the reference's host loop.
 """
 from __future__ import annotations
 
@@ -237,17 +241,24 @@ class _Ingest:
     ~1000 pairs/s while the captured pipeline does 2300-3400
     (tools/bench_host_pin.py, tools/bench_kitti_parts.py)."""
 
-    def __init__(self, pairs, device: torch.device, batch: int):
-        self.pairs, self.device, self.batch = iter(pairs), device, batch
+    def __init__(self, pairs, device: torch.device, batch: int, n_extra: int = 0):
+        self.pairs, self.device, self.batch, self.n_extra = iter(pairs), device, batch, n_extra
         self.copy_stream = torch.cuda.Stream(device=device)
         self.slots = [None, None]          # pinned host staging, allocated on first use per shape
         self.views = [None, None]          # the same memory as numpy arrays [2*batch, H, W, 3]
         self.uploaded = [None, None]       # event of the last upload that read each staging buffer
+        # n_extra > 0: every item is (img1, img2, e_0 .. e_{n_extra-1}), the e_k numpy arrays of one shape and dtype per k (the
+        # ground truth of evaluate_stream); they are staged and uploaded with the images and handed out by batches_with_extra()
+        self.xslots = [None, None]         # per staging buffer: pinned tensors [batch, *e_k.shape]
+        self.xviews = [None, None]
 
     def _fill(self, slot: int):
-        imgs = []
-        for a, b in self.pairs:
-            a, b = _host_u8(a), _host_u8(b)
+        imgs, extras = [], []
+        for item in self.pairs:
+            a, b = _host_u8(item[0]), _host_u8(item[1])
+            if len(item) != 2 + self.n_extra:
+                raise ValueError("an item must be (img1, img2) plus %d extra arrays, got %d entries" % (self.n_extra, len(item)))
+            extras.append(item[2:])
             if tuple(b.shape[:2]) != tuple(a.shape[:2]) or (imgs and tuple(a.shape[:2]) != tuple(imgs[0].shape[:2])):
                 raise ValueError("a batch needs uint8 [H,W,>=3] images of one size")
             imgs += [a, b]
@@ -264,22 +275,37 @@ class _Ingest:
             self.uploaded[slot].synchronize()      # the DMA that last read this buffer must be done before it is rewritten
         for i, img in enumerate(imgs):             # straight into pinned memory (an intermediate torch.stack cost 5 ms/pair)
             np.copyto(self.views[slot][i], img.numpy()[..., :3])
+        if self.n_extra:
+            first = [np.asarray(e) for e in extras[0]]
+            if self.xslots[slot] is None or any(tuple(t.shape[1:]) != e.shape for t, e in zip(self.xslots[slot], first)):
+                self.xslots[slot] = [torch.from_numpy(np.empty((self.batch,) + e.shape, e.dtype)).pin_memory() for e in first]
+                self.xviews[slot] = [t.numpy() for t in self.xslots[slot]]
+            for i, ex in enumerate(extras):
+                for view, e in zip(self.xviews[slot], ex):
+                    np.copyto(view[i], e, casting="no")
         with torch.cuda.stream(self.copy_stream):
             dev = self.slots[slot][:n].to(self.device, non_blocking=True)
+            xdev = tuple(t[:n].to(self.device, non_blocking=True) for t in self.xslots[slot]) if self.n_extra else ()
             ev = torch.cuda.Event()
             ev.record(self.copy_stream)
         self.uploaded[slot] = ev
-        return dev, ev
+        return dev, ev, xdev
 
-    def batches(self) -> Iterator[torch.Tensor]:
+    def batches_with_extra(self) -> Iterator[Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]]:
         pending, slot = self._fill(0), 1
         while pending is not None:
-            dev, ev = pending
+            dev, ev, xdev = pending
             pending = self._fill(slot)             # batch k+1 is staged and its upload started before batch k is consumed
             slot ^= 1
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             dev.record_stream(cur)
+            for t in xdev:
+                t.record_stream(cur)
+            yield dev, xdev
+
+    def batches(self) -> Iterator[torch.Tensor]:
+        for dev, _ in self.batches_with_extra():
             yield dev
 
 
@@ -309,7 +335,7 @@ class GraphedInfer:
         self.model, self.reference_unpad, self.batch = model, reference_unpad, batch
         self.static_u8 = torch.zeros((batch, 2, height, width, 3), dtype=torch.uint8, device=device)
         self.x_in = torch.empty((batch, 6, (height + 63) // 64 * 64, (width + 63) // 64 * 64), dtype=torch.float32, device=device)
-        self.flow_full = torch.empty((batch, 2, height, width), dtype=torch.float32, device=device)
+        self._alloc_outputs(height, width, device)
         keep, model.use_graph = getattr(model, "use_graph", False), False      # no nested capture
         try:
             side = torch.cuda.Stream(device=device)
@@ -322,6 +348,13 @@ class GraphedInfer:
                 self.out = self._body()
         finally:
             model.use_graph = keep
+
+    def _alloc_outputs(self, height: int, width: int, device) -> None:
+        self.flow_full = torch.empty((self.batch, 2, height, width), dtype=torch.float32, device=device)
+
+    def _tail(self, ch: int, cw: int, h: int, w: int) -> torch.Tensor:
+        """Last kernel of the captured pipeline: quarter-resolution flow -> what the graph hands out (ScoredInfer scores here instead)."""
+        return ops.flow_upsample(self.flow_quarter, ch, cw, h, w, out=self.flow_full)
 
     def _body(self) -> torch.Tensor:
         h, w = self.static_u8.shape[2:4]
@@ -342,7 +375,8 @@ class GraphedInfer:
         self.flow_quarter = out[0] if isinstance(out, (tuple, list)) else out
         hq, wq = self.flow_quarter.shape[-2:]
         ch, cw = (hq - ph, wq - pw) if self.reference_unpad else (hq - ph // 4, wq - pw // 4)
-        return ops.flow_upsample(self.flow_quarter, ch, cw, h, w, out=self.flow_full)
+        self.crop = (ch, cw)                       # the top-left part of flow_quarter that is stretched to (h, w)
+        return self._tail(ch, cw, h, w)
 
     def __call__(self, pair_u8: torch.Tensor) -> torch.Tensor:
         """pair_u8: [2,H,W,3] (one pair) or [n,2,H,W,3] with n <= batch; returns the first n flows [n,2,H,W]."""
@@ -377,6 +411,129 @@ def evaluate_pairs(model, samples: Iterable[Tuple[torch.Tensor, torch.Tensor, np
     if not rows:
         return float("nan"), float("nan"), rows
     return float(np.nanmean([r[0] for r in rows])), float(np.nanmean([r[1] for r in rows])), rows
+
+
+class ScoredInfer(GraphedInfer):
+    """GraphedInfer's graph with the score kernel in place of the upsample kernel: ingest -> forward -> ops.kitti_score, for one
+    fixed image size and one ground-truth form.
+
+    gt="png16": the ground truth is the KITTI PNG samples, uint16 [n,H,W,3] (R G B, what read_png16_rgb returns; 6 B/px);
+    gt="float": float32 planes [n,2,H,W] plus uint8 validity [n,H,W] (9 B/px).  The graph reads static buffers of both the
+    uint8 pairs and the ground truth.  keep_flow=False (default): no full-resolution flow exists anywhere; keep_flow=True also
+    fills ``flow_full`` [batch,2,H,W] (for callers who save the flow as well).  ``__call__(pairs_u8, gt, row0)`` replays the graph
+    and copies the batch's raw totals {fp64 sum of EPE, int64 #valid, int64 #outliers} into rows row0.. of ``table`` (int64
+    [rows,3] on the device, allocated once for the whole dataset); nothing synchronises -- download the table once at the end
+    (``results()``)."""
+
+    def __init__(self, model, height: int, width: int, device: torch.device, reference_unpad: bool = True, batch: int = 1,
+                 gt: str = "png16", rows: int = 0, keep_flow: bool = False):
+        if gt not in ("png16", "float"):
+            raise ValueError("gt must be 'png16' or 'float', got %r" % (gt,))
+        if os.environ.get("PWC_KITTI_TORCH_PREPOST") == "1":
+            raise ValueError("ScoredInfer has no PyTorch pre/post-processing variant (unset PWC_KITTI_TORCH_PREPOST)")
+        self.gt_form, self.keep_flow = gt, keep_flow
+        if gt == "png16":
+            self.static_gt = (torch.zeros((batch, height, width, 3), dtype=torch.uint16, device=device),)
+        else:
+            self.static_gt = (torch.zeros((batch, 2, height, width), dtype=torch.float32, device=device),
+                              torch.zeros((batch, height, width), dtype=torch.uint8, device=device))
+        self.table = torch.zeros((max(int(rows), batch), 3), dtype=torch.int64, device=device)
+        super().__init__(model, height, width, device, reference_unpad=reference_unpad, batch=batch)
+
+    def _alloc_outputs(self, height: int, width: int, device) -> None:
+        self.flow_full = torch.empty((self.batch, 2, height, width), dtype=torch.float32, device=device) if self.keep_flow else None
+        self.scores = torch.empty((self.batch, 2), dtype=torch.float32, device=device)
+
+    def _tail(self, ch: int, cw: int, h: int, w: int) -> torch.Tensor:
+        valid = self.static_gt[1] if self.gt_form == "float" else None
+        _, s, nv, no = ops.kitti_score(self.flow_quarter, ch, cw, h, w, self.static_gt[0], valid=valid, flow_out=self.flow_full,
+                                       out=self.scores, raw=True)
+        # the three columns are views of the [batch,3] head of ops.kitti_score's cached workspace: the same memory as one int64 table
+        # (the fp64 sums as their bit patterns), so the graph needs no kernel to gather them
+        self.totals = torch.as_strided(nv, (self.batch, 3), (3, 1), nv.storage_offset() - 1)
+        return self.scores
+
+    def __call__(self, pairs_u8: torch.Tensor, gt, row0: int) -> torch.Tensor:
+        """pairs_u8 [n<=batch,2,H,W,3] uint8 and the ground truth of those n pairs on the device (a uint16 tensor, or (flow planes,
+        validity)); fills table[row0:row0+n] and returns the float32 scores [n,2] = (EPE, Fl-all) (a static buffer)."""
+        gt = tuple(gt) if isinstance(gt, (tuple, list)) else (gt,)
+        n = pairs_u8.shape[0]
+        if pairs_u8.dim() != 5 or tuple(pairs_u8.shape[1:]) != tuple(self.static_u8.shape[1:]) or pairs_u8.dtype != torch.uint8 \
+                or not 1 <= n <= self.batch:
+            raise ValueError("expected uint8 [n<=%d,%s], got %s %s" % (self.batch, ",".join(map(str, self.static_u8.shape[1:])),
+                                                                      pairs_u8.dtype, tuple(pairs_u8.shape)))
+        if len(gt) != len(self.static_gt) or any(tuple(g.shape) != (n,) + tuple(st.shape[1:]) for g, st in zip(gt, self.static_gt)):
+            raise ValueError("ground truth does not match the %r form %s of this pipeline" % (self.gt_form, [tuple(st.shape[1:]) for st in self.static_gt]))
+        if not 0 <= row0 <= self.table.shape[0] - n:
+            raise ValueError("rows %d..%d do not fit the result table of %d rows" % (row0, row0 + n, self.table.shape[0]))
+        self.static_u8[:n].copy_(pairs_u8, non_blocking=True)
+        for st, g in zip(self.static_gt, gt):
+            st[:n].copy_(g.view(torch.uint8) if g.dtype == torch.bool else g, non_blocking=True)
+        self.graph.replay()
+        self.table[row0:row0 + n].copy_(self.totals[:n], non_blocking=True)
+        return self.out[:n]
+
+    def results(self, rows: Optional[int] = None):
+        """ONE download of the table (this synchronises): float64 (sum_epe [rows], n_valid, n_outlier) numpy arrays."""
+        tab = self.table[:rows].cpu()
+        return tab[:, 0].contiguous().view(torch.float64).numpy(), tab[:, 1].numpy().astype(np.float64), tab[:, 2].numpy().astype(np.float64)
+
+
+def rows_from_totals(sum_epe, n_valid, n_outlier):
+    """Per-sample (EPE, Fl-all in percent) in float64 from the raw totals; (nan, nan) for a sample without a valid pixel
+    (epe_metric / fl_all_metric return np.nan there)."""
+    rows = []
+    for s, nv, no in zip(sum_epe, n_valid, n_outlier):
+        rows.append((float(s) / float(nv), 100.0 * float(no) / float(nv)) if nv else (float("nan"), float("nan")))
+    return rows
+
+
+def _nanmean_rows(rows):
+    if all(np.isnan(r[0]) for r in rows):
+        return float("nan"), float("nan")
+    return float(np.nanmean([r[0] for r in rows])), float(np.nanmean([r[1] for r in rows]))
+
+
+def evaluate_stream(model, samples, device: torch.device, batch: int = 16, reference_unpad: bool = True,
+                    pipe: Optional["ScoredInfer"] = None):
+    """evaluate_pairs without the host in the loop: samples (img1_u8 [H,W,3], img2_u8, gt) of one size, gt either the uint16
+    [H,W,3] array read_png16_rgb returns or (flow [H,W,2] float32, valid [H,W] bool) -- one form per call.  Images and ground
+    truth are staged together in pinned double buffers and uploaded on the copy stream; one graph replay (ScoredInfer) per batch,
+    no per-batch synchronisation; ONE download of the [N,3] totals at the end, from which the per-sample EPE and Fl-all are formed
+    on the host in float64.  Returns (mean EPE, mean Fl-all, rows) with evaluate_pairs' nanmean semantics.  `pipe`: a ScoredInfer
+    built for this size, batch and ground-truth form to reuse (its capture costs more than a short evaluation)."""
+    samples = list(samples)
+    if not samples:
+        return float("nan"), float("nan"), []
+    png = not isinstance(samples[0][2], (tuple, list))
+    h, w = _host_u8(samples[0][0]).shape[:2]
+    if pipe is None:
+        pipe = ScoredInfer(model, h, w, device, reference_unpad=reference_unpad, batch=batch, gt="png16" if png else "float",
+                           rows=len(samples))
+    elif pipe.gt_form != ("png16" if png else "float") or pipe.table.shape[0] < len(samples):
+        raise ValueError("pipe was built for another ground-truth form or fewer rows")
+
+    def items():
+        for s in samples:
+            if isinstance(s[2], (tuple, list)) == png:
+                raise ValueError("one ground-truth form per call")
+            if png:
+                g = np.asarray(s[2])
+                if g.dtype != np.uint16 or g.shape != (h, w, 3):
+                    raise ValueError("uint16 ground truth must be [%d,%d,3], got %s %s" % (h, w, g.dtype, g.shape))
+                yield s[0], s[1], g
+            else:
+                f, v = np.asarray(s[2][0]), np.asarray(s[2][1])
+                if f.dtype != np.float32 or f.shape != (h, w, 2) or v.shape != (h, w) or v.dtype not in (np.bool_, np.uint8):
+                    raise ValueError("float ground truth must be (float32 [%d,%d,2], bool [%d,%d])" % (h, w, h, w))
+                yield s[0], s[1], f.transpose(2, 0, 1), v.view(np.uint8)
+
+    row0 = 0
+    for dev, gt in _Ingest(items(), device, pipe.batch, n_extra=1 if png else 2).batches_with_extra():
+        pipe(dev, gt, row0)
+        row0 += dev.shape[0]
+    rows = rows_from_totals(*pipe.results(len(samples)))
+    return _nanmean_rows(rows) + (rows,)
 
 
 # ------------------------------------------------------------------ the stream sharded over the GPUs of one node
@@ -418,15 +575,22 @@ class ShardedStream:
         self.infer = infer
         self.batcher = batcher or BatchStream
         self._gathers = {}
+        self.score_geometry = None         # for_model(score=True): (crop_h, crop_w, H, W) of the pipeline's quarter-resolution flow
+        self.last_quarter = None           # ... and the quarter-resolution flows of the step run() handed out last
 
     @classmethod
-    def for_model(cls, model, height: int, width: int, device, batch: int = 1, reference_unpad: bool = True, **kw):
+    def for_model(cls, model, height: int, width: int, device, batch: int = 1, reference_unpad: bool = True, score: bool = False, **kw):
+        """score=True lets evaluate_pairs_sharded(route="hip") score from the quarter-resolution flow (it records the crop geometry and,
+        per step, that flow); the pipeline and what run() yields are the same either way."""
         pipe = GraphedInfer(model, height, width, device, reference_unpad=reference_unpad, batch=batch)
 
         def infer(u8):
             full = pipe(u8)
             return full, pipe.flow_quarter[:u8.shape[0]]
-        return cls(device, batch=batch, infer=infer, **kw)
+        self = cls(device, batch=batch, infer=infer, **kw)
+        if score:
+            self.score_geometry = pipe.crop + (height, width)
+        return self
 
     def my_indices(self, n_items: int):
         return range(self.rank, n_items, self.world)
@@ -461,6 +625,8 @@ class ShardedStream:
             if n:
                 full, quarter = self.infer(next(batches))
                 tail = (tuple(quarter.shape[1:]), quarter.dtype, quarter.device)
+            if self.score_geometry is not None:
+                self.last_quarter = quarter
             gathered = None
             if self.gather and self.world > 1:
                 if quarter is None:                      # a rank that ran out of pairs still joins the collective
@@ -476,20 +642,45 @@ class ShardedStream:
             yield idx, full, gathered
 
 
-def evaluate_pairs_sharded(stream: "ShardedStream", samples, group=None):
+def evaluate_pairs_sharded(stream: "ShardedStream", samples, group=None, route: str = "host"):
     """inference_kitti.py:296-314 over a sharded stream: each rank scores the pairs it processed against their ground
     truth (samples[i] = (img1_u8, img2_u8, flow_gt [H,W,2], valid [H,W])); only three numbers per rank travel:
-    (sum EPE, sum Fl-all, count).  Returns (mean EPE, mean Fl-all, n) on every rank."""
+    (sum EPE, sum Fl-all, count).  Returns (mean EPE, mean Fl-all, n) on every rank.
+    route="host": every full-resolution flow is downloaded and scored with NumPy (the reference's loop).  route="hip": each rank
+    scores its pairs with ops.kitti_score from the quarter-resolution flow its pipeline already holds (a stream made by
+    ShardedStream.for_model(..., score=True)); per rank only the [n,3] totals are downloaded, once, after the last step."""
     import torch.distributed as dist
+    if route not in ("host", "hip"):
+        raise ValueError("route must be 'host' or 'hip', got %r" % (route,))
+    if route == "hip" and stream.score_geometry is None:
+        raise ValueError("route='hip' needs a stream made by ShardedStream.for_model(..., score=True)")
     acc = torch.zeros(3, dtype=torch.float64)
     keep, stream.gather = stream.gather, False
     try:
-        for idx, full, _ in stream.run([(s[0], s[1]) for s in samples]):
-            for k, i in enumerate(idx):
-                fp = full[k].permute(1, 2, 0).cpu().numpy()
-                e, f = epe_metric(fp, samples[i][2], samples[i][3]), fl_all_metric(fp, samples[i][2], samples[i][3])
-                if not (np.isnan(e) or np.isnan(f)):
-                    acc += torch.tensor([e, f, 1.0], dtype=torch.float64)
+        if route == "hip":
+            ch, cw, h, w = stream.score_geometry
+            totals = []
+            for idx, _, _ in stream.run([(s[0], s[1]) for s in samples]):
+                if not idx:
+                    continue
+                gt = torch.from_numpy(np.ascontiguousarray(np.stack([np.asarray(samples[i][2], dtype=np.float32).transpose(2, 0, 1) for i in idx])))
+                valid = torch.from_numpy(np.stack([np.asarray(samples[i][3]).astype(np.uint8) for i in idx]))
+                _, s_, nv, no = ops.kitti_score(stream.last_quarter, ch, cw, h, w, gt.to(stream.device), valid=valid.to(stream.device),
+                                                raw=True)
+                totals.append(torch.stack((s_.view(torch.int64), nv, no), dim=1))
+            if totals:
+                tab = torch.cat(totals).cpu()                                  # the one download (and synchronisation) of this rank
+                rows = rows_from_totals(tab[:, 0].contiguous().view(torch.float64).numpy(), tab[:, 1].numpy(), tab[:, 2].numpy())
+                for e, f in rows:
+                    if not (np.isnan(e) or np.isnan(f)):
+                        acc += torch.tensor([e, f, 1.0], dtype=torch.float64)
+        else:
+            for idx, full, _ in stream.run([(s[0], s[1]) for s in samples]):
+                for k, i in enumerate(idx):
+                    fp = full[k].permute(1, 2, 0).cpu().numpy()
+                    e, f = epe_metric(fp, samples[i][2], samples[i][3]), fl_all_metric(fp, samples[i][2], samples[i][3])
+                    if not (np.isnan(e) or np.isnan(f)):
+                        acc += torch.tensor([e, f, 1.0], dtype=torch.float64)
     finally:
         stream.gather = keep
     if dist.is_initialized() and stream.world > 1:

@@ -604,6 +604,73 @@ def flow_upsample(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, ou
     return out
 
 
+def kitti_score_workspace_bytes(n: int, out_h: int, out_w: int) -> int:
+    nb = _lib.load().pwc_kitti_score_workspace_bytes(n, out_h, out_w)
+    if nb < 0:
+        raise ValueError("bad kitti-score geometry")
+    return int(nb)
+
+
+_SCORE_WS = {}
+
+
+def kitti_score(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, out_w: int, gt: torch.Tensor,
+                valid: Optional[torch.Tensor] = None, flow_out: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                raw: bool = False):
+    """float32 [n,2] = per-sample (EPE, Fl-all in percent) of pwc_kitti_score: the quarter-resolution flow [n,2,Hq,Wq] is cropped and
+    upsampled exactly as `flow_upsample` does and scored against the ground truth in the same pass (epe_metric / fl_all_metric of
+    inference_kitti.py:94-128); NaN for a sample without a valid pixel.  gt: torch.uint16 [n,out_h,out_w,3] (the KITTI PNG samples, R G
+    B; validity is the blue sample, `valid` must be None) or float32 [n,2,out_h,out_w] with `valid` None / bool or uint8 [n,out_h,out_w].
+    flow_out: optional float32 [n,2,out_h,out_w] that also receives the full-resolution flow.  raw=True returns (out, sum_epe float64
+    [n], n_valid int64 [n], n_outlier int64 [n]): views of the workspace, which is cached per (device, shape) -- consume them before the
+    next call of that shape.  Device tensors only, no host synchronisation, bit-reproducible."""
+    if not flow_q.is_cuda or flow_q.dtype != torch.float32 or flow_q.dim() != 4 or flow_q.shape[1] != 2:
+        raise ValueError("flow_q must be a float32 device tensor [n,2,Hq,Wq]")
+    n, _, Hq, Wq = flow_q.shape
+    dev = flow_q.device
+    bsq = _plane_dense(flow_q, "flow_q")
+    out_h, out_w = int(out_h), int(out_w)
+    if gt.device != dev or not gt.is_contiguous():
+        raise ValueError("gt must be a contiguous tensor on %s" % dev)
+    if gt.dtype == torch.uint16:
+        kind, want = 1, (n, out_h, out_w, 3)
+        if valid is not None:
+            raise ValueError("valid must be None with uint16 ground truth (the blue sample is the validity)")
+    elif gt.dtype == torch.float32:
+        kind, want = 0, (n, 2, out_h, out_w)
+        if valid is not None:
+            if valid.dtype == torch.bool:
+                valid = valid.view(torch.uint8)
+            if valid.dtype != torch.uint8 or tuple(valid.shape) != (n, out_h, out_w) or valid.device != dev or not valid.is_contiguous():
+                raise ValueError("valid must be a contiguous bool / uint8 %s tensor on %s" % ((n, out_h, out_w), dev))
+    else:
+        raise ValueError("gt must be torch.uint16 [n,H,W,3] or float32 [n,2,H,W], got %s" % gt.dtype)
+    if tuple(gt.shape) != want:
+        raise ValueError("gt must be %s %s, got %s" % (gt.dtype, want, tuple(gt.shape)))
+    if flow_out is not None and (tuple(flow_out.shape) != (n, 2, out_h, out_w) or flow_out.dtype != torch.float32 or flow_out.device != dev
+                                 or not flow_out.is_contiguous()):
+        raise ValueError("flow_out must be contiguous float32 %s on %s" % ((n, 2, out_h, out_w), dev))
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+        raise ValueError("out must be a contiguous float32 %s tensor on %s" % ((n, 2), dev))
+    with torch.cuda.device(dev):
+        nb = kitti_score_workspace_bytes(max(n, 1), max(out_h, 1), max(out_w, 1))
+        key = (dev, n, out_h, out_w)
+        ws = _SCORE_WS.get(key)
+        if ws is None:
+            ws = _SCORE_WS[key] = torch.empty(nb // 8, dtype=torch.int64, device=dev)
+        rc = _lib.load().pwc_kitti_score(flow_q.data_ptr(), n, Hq, Wq, int(crop_h), int(crop_w), out_h, out_w, bsq, gt.data_ptr(), kind,
+                                         valid.data_ptr() if valid is not None else None,
+                                         flow_out.data_ptr() if flow_out is not None else None, ws.data_ptr(), nb, out.data_ptr(),
+                                         _stream(flow_q))
+    check(rc, "pwc_kitti_score")
+    if raw:
+        head = ws[:3 * n].view(n, 3)
+        return out, head[:, 0].view(torch.float64), head[:, 1], head[:, 2]
+    return out
+
+
 def lattice_unsplit(x: torch.Tensor, batch: int, levels: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Inverse of `levels` nested split2 stores: [batch * 4**levels, C, h, w] (contiguous) -> [batch, C, h << levels, w << levels]."""
     if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4 or x.shape[0] != batch * 4 ** levels:
