@@ -7,6 +7,7 @@
 #include <stdarg.h>
 
 #include <atomic>
+#include <initializer_list>
 
 #include "../../include/pwc_hip.h"
 
@@ -47,6 +48,20 @@ __device__ __forceinline__ _Float16 sat_half(float v) {
 }
 
 inline bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+
+// true when one of the pointers is not a multiple of `a` bytes (a power of two); null pointers pass
+inline bool misaligned(std::initializer_list<const void *> ps, uintptr_t a = 4) {
+    uintptr_t al = 0;
+    for (const void *p : ps) al |= reinterpret_cast<uintptr_t>(p);
+    return (al & (a - 1)) != 0;
+}
+
+// value of an optional per-pixel mask (float32, or bytes when mask_u8) at element `off`; 1 without a mask
+__device__ __forceinline__ float mask_val(const void *mask, int mask_u8, int64_t off) {
+    if (!mask) return 1.0f;
+    if (mask_u8) return (float)static_cast<const unsigned char *>(mask)[off];
+    return static_cast<const float *>(mask)[off];
+}
 
 // Raise a kernel's dynamic-LDS limit once per (kernel instantiation, device).  `done` is a per-instantiation
 // static array; relaxed atomics are enough (setting the attribute twice is harmless).

@@ -29,9 +29,9 @@
 // Quantiles.  For d >= 0 the fp64 bit pattern orders like the value, so numpy's linear quantile (virtual index (n-1) q, then
 // _lerp(a, b, g) = a + (b-a) g, or b - (b-a)(1-g) when g >= 0.5) takes two order statistics, found by an 8-bit radix select over
 // the finite d of one sample in one workgroup (four ranks at once: keep_ratio's and min_keep's two each).
+#include "pwc_block_reduce.h"
 #include "pwc_common.h"
 
-#include <initializer_list>
 #include <math.h>
 
 namespace {
@@ -39,7 +39,7 @@ namespace {
 constexpr double kEps12 = 1e-12;
 constexpr int kScoreThreads = 256, kScorePts = 4, kScoreHyps = 64;
 constexpr int kRefitThreads = 256;
-constexpr int kSelThreads = 1024, kSelWaves = kSelThreads / 64;
+constexpr int kSelThreads = 1024;
 constexpr int kMapThreads = 256;
 constexpr int kLossThreads = 256, kLossPer = 8, kLossChunk = kLossThreads * kLossPer;
 
@@ -186,17 +186,8 @@ __device__ __forceinline__ void design_row(double x1a, double x1b, double x2a, d
 
 __device__ __forceinline__ double hom_w() { return 1.0 + kEps12; }
 
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ long long wave_sum_i(long long v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using pwc::misaligned;
+using pwc::wave_block_sum;   // pwc_block_reduce.h: per wave xor tree, then the waves in order: fixed order, bit-reproducible
 
 // ------------------------------------------------------------------------------------------------------------ compaction
 // one workgroup per sample; chunks of 1024 grid points in row-major order, ballot + wave prefix for the order-preserving write
@@ -221,10 +212,7 @@ __global__ __launch_bounds__(1024) void epi_pairs_kernel(const float *__restrict
             u2 = u + (double)fu[o];
             v2 = v + (double)fv[o];
             valid = finite64(u2) && finite64(v2);
-            if (mask) {
-                if (mask_u8) valid = valid && static_cast<const unsigned char *>(mask)[(int64_t)b * mask_bs + o] != 0;
-                else valid = valid && static_cast<const float *>(mask)[(int64_t)b * mask_bs + o] != 0.0f;
-            }
+            valid = valid && pwc::mask_val(mask, mask_u8, (int64_t)b * mask_bs + o) != 0.0f;
         }
         const unsigned long long bal = __ballot(valid);
         const int before = __popcll(bal & ((1ull << lane) - 1ull));
@@ -344,29 +332,11 @@ __global__ __launch_bounds__(kScoreThreads) void epi_score_kernel(const double *
 }
 
 // ------------------------------------------------------------------------------------------------------------ best + refit
-template <int K> __device__ __forceinline__ void block_sum(double (&v)[K], double *red, int tid) {
-    // per wave xor tree, then waves in order: fixed order, bit-reproducible
-    const int lane = tid & 63, wv = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < K; ++k) v[k] = wave_sum(v[k]);
-    __syncthreads();
-    if (lane == 0)
-#pragma unroll
-        for (int k = 0; k < K; ++k) red[wv * K + k] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < K; ++k) {
-        double s = red[k];
-        for (int o = 1; o < kRefitThreads / 64; ++o) s += red[o * K + k];
-        v[k] = s;
-    }
-}
-
 __global__ __launch_bounds__(kRefitThreads) void epi_refit_kernel(const double *__restrict__ pts, const int *__restrict__ npts, int cap,
                                                                  const double *__restrict__ Fh, const int *__restrict__ counts,
                                                                  int iters, double thresh, double *__restrict__ F_out,
                                                                  int *__restrict__ ok_out, int *__restrict__ best_out) {
-    __shared__ double red[(kRefitThreads / 64) * 45];
+    __shared__ pwc::WaveLds<double, kRefitThreads, 45> red;
     __shared__ int bc[kRefitThreads / 64], bi[kRefitThreads / 64];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int N = npts[b];
@@ -404,7 +374,7 @@ __global__ __launch_bounds__(kRefitThreads) void epi_refit_kernel(const double *
         const double a = P[4 * j] / w, bb = P[4 * j + 1] / w, e = P[4 * j + 2] / w, f = P[4 * j + 3] / w;
         if (sampson(Fb, a, bb, c, e, f, c) < thresh) { s4[0] += a; s4[1] += bb; s4[2] += e; s4[3] += f; s4[4] += 1.0; }
     }
-    block_sum<5>(s4, red, tid);
+    wave_block_sum(red, s4);
     const double n = s4[4];
     const double m1x = s4[0] / n, m1y = s4[1] / n, m2x = s4[2] / n, m2y = s4[3] / n;
     // pass 2: mean distances
@@ -417,7 +387,7 @@ __global__ __launch_bounds__(kRefitThreads) void epi_refit_kernel(const double *
             s2v[1] += sqrt(ex * ex + ey * ey) + kEps12;
         }
     }
-    block_sum<2>(s2v, red, tid);
+    wave_block_sum(red, s2v);
     const double s1 = 1.4142135623730951 / (s2v[0] / n), s2 = 1.4142135623730951 / (s2v[1] / n);
     // pass 3: Gram matrix of the normalised rows (upper triangle, 45 sums)
     double g[45];
@@ -435,7 +405,7 @@ __global__ __launch_bounds__(kRefitThreads) void epi_refit_kernel(const double *
                 for (int q = p; q < 9; ++q) g[k++] += r[p] * r[q];
         }
     }
-    block_sum<45>(g, red, tid);
+    wave_block_sum(red, g);
     if (tid != 0) return;
     double G[9][9];
     {
@@ -484,22 +454,12 @@ __device__ __forceinline__ double np_lerp(double a, double bv, double g) {
     return g >= 0.5 ? bv - diff * (1.0 - g) : a + diff * g;
 }
 
-__device__ __forceinline__ int64_t block_count(int64_t v, int64_t *redi, int tid) {
-    v = wave_sum_i(v);
-    __syncthreads();
-    if ((tid & 63) == 0) redi[tid >> 6] = v;
-    __syncthreads();
-    int64_t s = 0;
-    for (int k = 0; k < kSelWaves; ++k) s += redi[k];
-    return s;
-}
-
 // one workgroup per sample: finite count, radix select of up to four ranks, lerp, keep count, relaxation decision
 __global__ __launch_bounds__(kSelThreads) void epi_select_kernel(const double *__restrict__ dist, const int *__restrict__ ok,
                                                                 int64_t plane, SelCfg cfg, double *__restrict__ thr_out,
                                                                 int *__restrict__ all_out) {
     __shared__ unsigned hist[4][256];
-    __shared__ int64_t redi[kSelWaves];
+    __shared__ pwc::WaveLds<long long, kSelThreads> redi;
     __shared__ unsigned long long pre_s[4];
     __shared__ int64_t rank_s[4];
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -509,9 +469,10 @@ __global__ __launch_bounds__(kSelThreads) void epi_select_kernel(const double *_
         if (tid == 0) { thr_out[b] = __longlong_as_double(0x7ff8000000000000LL); all_out[b] = 1; }
         return;
     }
-    int64_t nf = 0;
-    for (int64_t o = tid; o < plane; o += kSelThreads) nf += finite64(d[o]) ? 1 : 0;
-    const int64_t nfin = block_count(nf, redi, tid);
+    long long nf[1] = {0};
+    for (int64_t o = tid; o < plane; o += kSelThreads) nf[0] += finite64(d[o]) ? 1 : 0;
+    wave_block_sum(redi, nf);
+    const int64_t nfin = nf[0];
     if (nfin == 0) {
         if (tid == 0) { thr_out[b] = __longlong_as_double(0x7ff8000000000000LL); all_out[b] = 1; }
         return;
@@ -585,13 +546,13 @@ __global__ __launch_bounds__(kSelThreads) void epi_select_kernel(const double *_
     double thr = cfg.tau;
     if (cfg.use_keep && qk < thr) thr = qk;
     if (cfg.use_min) {
-        int64_t kc = 0;
+        long long keep[1] = {0};
         for (int64_t o = tid; o < plane; o += kSelThreads) {
             const double v = d[o];
-            kc += (finite64(v) && v <= thr) ? 1 : 0;
+            keep[0] += (finite64(v) && v <= thr) ? 1 : 0;
         }
-        const int64_t keep = block_count(kc, redi, tid);
-        if ((double)keep / (double)plane < cfg.min_keep) thr = qm < cfg.tau ? qm : cfg.tau;
+        wave_block_sum(redi, keep);
+        if ((double)keep[0] / (double)plane < cfg.min_keep) thr = qm < cfg.tau ? qm : cfg.tau;
     }
     if (tid == 0) { thr_out[b] = thr; all_out[b] = 0; }
 }
@@ -651,51 +612,44 @@ __device__ __forceinline__ double robust_term(int robust, double d, double delta
     return d;
 }
 
-// workgroup (chunk, sample) writes {sum, count} of its 2048 pixels; fixed sequential-then-tree order
+// workgroup (chunk, sample) writes {sum, count} of its 2048 pixels; fixed sequential-then-tree order.  wave_block_sum starts the
+// sum over the waves at the first wave's value and not at +0.0: the same bits, because a sum is -0.0 only when both terms are, every
+// lane (here and in the finish kernel) starts from +0.0, and so no lane's sum, no wave's and no partial is ever -0.0.
 __global__ __launch_bounds__(kLossThreads) void epi_loss_partial_kernel(LossArgs a, double *__restrict__ part) {
-    __shared__ double rs[kLossThreads / 64], rc[kLossThreads / 64];
+    __shared__ pwc::WaveLds<double, kLossThreads, 2> red;
     const int b = blockIdx.y, tid = threadIdx.x;
     const int64_t plane = (int64_t)a.H * a.W;
     double Fr[9];
     loss_F(a, b, Fr);
     const float *fu = a.flow + (int64_t)b * a.flow_bs;
-    double s = 0.0, n = 0.0;
+    double v[2] = {0.0, 0.0};   // sum, count
     for (int k = 0; k < kLossPer; ++k) {
         const int64_t o = (int64_t)blockIdx.x * kLossChunk + k * kLossThreads + tid;
         if (o >= plane || !loss_sel(a, b, o)) continue;
         const int y = (int)(o / a.W), x = (int)(o % a.W);
         const double d = sampson(Fr, (double)x, (double)y, 1.0, (double)((float)x + fu[o]), (double)((float)y + fu[plane + o]), 1.0);
         double g;
-        s += robust_term(a.robust, d, a.delta, &g);
-        n += 1.0;
+        v[0] += robust_term(a.robust, d, a.delta, &g);
+        v[1] += 1.0;
     }
-    s = wave_sum(s);
-    n = wave_sum(n);
-    if ((tid & 63) == 0) { rs[tid >> 6] = s; rc[tid >> 6] = n; }
-    __syncthreads();
+    wave_block_sum(red, v);
     if (tid == 0) {
-        double S = 0.0, C = 0.0;
-        for (int k = 0; k < kLossThreads / 64; ++k) { S += rs[k]; C += rc[k]; }
         const int64_t pi = (int64_t)b * gridDim.x + blockIdx.x;
-        part[2 * pi] = S;
-        part[2 * pi + 1] = C;
+        part[2 * pi] = v[0];
+        part[2 * pi + 1] = v[1];
     }
 }
 
 // one workgroup: partials in a fixed order -> out (float loss) and tot = {sum, count} (fp64, for the backward)
 __global__ __launch_bounds__(kLossThreads) void epi_loss_finish_kernel(const double *__restrict__ part, int64_t np, double weight,
                                                                       float *__restrict__ out, double *__restrict__ tot) {
-    __shared__ double rs[kLossThreads / 64], rc[kLossThreads / 64];
+    __shared__ pwc::WaveLds<double, kLossThreads, 2> red;
     const int tid = threadIdx.x;
-    double s = 0.0, n = 0.0;
-    for (int64_t i = tid; i < np; i += kLossThreads) { s += part[2 * i]; n += part[2 * i + 1]; }
-    s = wave_sum(s);
-    n = wave_sum(n);
-    if ((tid & 63) == 0) { rs[tid >> 6] = s; rc[tid >> 6] = n; }
-    __syncthreads();
+    double v[2] = {0.0, 0.0};
+    for (int64_t i = tid; i < np; i += kLossThreads) { v[0] += part[2 * i]; v[1] += part[2 * i + 1]; }
+    wave_block_sum(red, v);
     if (tid == 0) {
-        double S = 0.0, C = 0.0;
-        for (int k = 0; k < kLossThreads / 64; ++k) { S += rs[k]; C += rc[k]; }
+        const double S = v[0], C = v[1];
         if (out) out[0] = C > 0.0 ? (float)(weight * (S / C)) : 0.0f;
         if (tot) { tot[0] = S; tot[1] = C; }
     }
@@ -732,12 +686,6 @@ __global__ __launch_bounds__(kLossThreads) void epi_loss_bwd_kernel(LossArgs a, 
     const double gy = 2.0 * n * f1 / den - q * (2.0 * t0 * F[3] + 2.0 * t1 * F[4]);
     gu[o] = (float)(sc * gx);
     gu[plane + o] = (float)(sc * gy);
-}
-
-bool misaligned(std::initializer_list<const void *> ps, uintptr_t a) {
-    for (const void *p : ps)
-        if (p && (reinterpret_cast<uintptr_t>(p) & (a - 1))) return true;
-    return false;
 }
 
 int64_t pad8(int64_t n) { return (n + 7) & ~7LL; }

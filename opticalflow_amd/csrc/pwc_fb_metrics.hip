@@ -17,6 +17,7 @@
 // no window of it is known before a.  Nothing image-sized is written: each workgroup leaves {fp64 cycle sum,
 // int64 oob count} (fixed tree order) in the workspace and one final workgroup adds them in workgroup order.  No atomics: the
 // result is bit-reproducible.
+#include "pwc_block_reduce.h"
 #include "pwc_common.h"
 #include "pwc_flow_up.h"
 
@@ -25,36 +26,17 @@ namespace {
 constexpr int kTH = 16, kTW = 64, kThreads = 256;
 constexpr int kRowStep = kThreads / kTW;      // 4
 constexpr int kPix = kTH / kRowStep;          // 4 pixels per lane
-constexpr int64_t kHead = 16;                 // workspace bytes in front of the partials: {double cycle_sum, int64 oob_count}
+using Rec = pwc::TilePartial<1>;               // {double cycle_sum, int64 oob_count}: workspace = the total, then one per tile
 
-struct Geo {
-    int B, H, W, h, w, tiles_x, tiles_y, same;
-    float rh, rw, sy, sx;
+struct Geo : pwc::UpGeo {
+    int B, tiles_x, tiles_y;
     int64_t bs12, bs21;
 };
 
 using pwc::up_flow;   // pwc_flow_up.h: upsampled flow (u, v) at full-resolution pixel (Y, X)
 
-// fixed-order block sum of one double and one 64-bit count per lane; result valid in lane 0
-__device__ __forceinline__ void block_sum(double &c, long long &n, double *red_c, long long *red_n) {
-    const int tid = threadIdx.x;
-    red_c[tid] = c;
-    red_n[tid] = n;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-            red_c[tid] += red_c[tid + s];
-            red_n[tid] += red_n[tid + s];
-        }
-        __syncthreads();
-    }
-    c = red_c[0];
-    n = red_n[0];
-}
-
-__global__ __launch_bounds__(kThreads) void fb_tile_kernel(const float *flow12, const float *flow21, char *part, Geo g) {
-    __shared__ double red_c[kThreads];
-    __shared__ long long red_n[kThreads];
+__global__ __launch_bounds__(kThreads) void fb_tile_kernel(const float *flow12, const float *flow21, Rec *part, Geo g) {
+    __shared__ pwc::TreeLds<kThreads, 1, 1> red;
     const int tid = threadIdx.x, b = blockIdx.z;
     const int col = tid % kTW, row0 = tid / kTW;
     const float *f12 = flow12 + (int64_t)b * g.bs12;
@@ -82,30 +64,27 @@ __global__ __launch_bounds__(kThreads) void fb_tile_kernel(const float *flow12, 
         const float wy = (1.0f - ty) * ((1.0f - tx) * v00.y + tx * v01.y) + ty * ((1.0f - tx) * v10.y + tx * v11.y);
         cyc += (double)(fabsf(a.x + wx) + fabsf(a.y + wy));
     }
-    block_sum(cyc, oob, red_c, red_n);
+    pwc::tree_sum(red, &cyc, &oob);
     if (tid == 0) {
         const int64_t lin = blockIdx.x + (int64_t)g.tiles_x * (blockIdx.y + (int64_t)g.tiles_y * blockIdx.z);
-        *reinterpret_cast<double *>(part + lin * 16) = cyc;
-        *reinterpret_cast<long long *>(part + lin * 16 + 8) = oob;
+        part[lin] = Rec{cyc, {oob}};
     }
 }
 
-__global__ __launch_bounds__(kThreads) void fb_finish_kernel(char *ws, int64_t nblk, int with_cycle, double ncycle, double npix,
+__global__ __launch_bounds__(kThreads) void fb_finish_kernel(Rec *ws, int64_t nblk, int with_cycle, double ncycle, double npix,
                                                              float *out) {
-    __shared__ double red_c[kThreads];
-    __shared__ long long red_n[kThreads];
+    __shared__ pwc::TreeLds<kThreads, 1, 1> red;
     const int tid = threadIdx.x;
-    const char *part = ws + kHead;
+    const Rec *part = ws + 1;
     double c = 0.0;
     long long n = 0;
     for (int64_t i = tid; i < nblk; i += kThreads) {
-        c += *reinterpret_cast<const double *>(part + i * 16);
-        n += *reinterpret_cast<const long long *>(part + i * 16 + 8);
+        c += part[i].sum;
+        n += part[i].count[0];
     }
-    block_sum(c, n, red_c, red_n);
+    pwc::tree_sum(red, &c, &n);
     if (tid == 0) {
-        *reinterpret_cast<double *>(ws) = c;
-        *reinterpret_cast<long long *>(ws + 8) = n;
+        ws[0] = Rec{c, {n}};
         out[0] = with_cycle ? (float)(c / ncycle) : 0.0f;
         out[1] = (float)((double)n / npix);
     }
@@ -115,7 +94,7 @@ __global__ __launch_bounds__(kThreads) void fb_finish_kernel(char *ws, int64_t n
 
 extern "C" int64_t pwc_fb_metrics_workspace_bytes(int B, int H, int W) {
     if (B <= 0 || H <= 0 || W <= 0) return -1;
-    return kHead + (int64_t)B * ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW) * 16;
+    return (int64_t)sizeof(Rec) * (1 + (int64_t)B * ((H + kTH - 1) / kTH) * ((W + kTW - 1) / kTW));
 }
 
 extern "C" int pwc_fb_metrics(const void *flow12, const void *flow21, int B, int h, int w, int H, int W,
@@ -130,27 +109,23 @@ extern "C" int pwc_fb_metrics(const void *flow12, const void *flow21, int B, int
         PWC_FAIL(PWC_EINVAL, "pwc_fb_metrics: needs B*2*H*W < 2^31, B <= 65535 and H <= 16 * 65535");
     if (flow12_bstride < 2LL * h * w || (flow21 && flow21_bstride < 2LL * h * w))
         PWC_FAIL(PWC_EINVAL, "pwc_fb_metrics: batch stride smaller than the tensor");
-    if (((reinterpret_cast<uintptr_t>(flow12) | reinterpret_cast<uintptr_t>(flow21) | reinterpret_cast<uintptr_t>(out2)) & 3u) != 0)
+    if (pwc::misaligned({flow12, flow21, out2}))
         PWC_FAIL(PWC_EINVAL, "pwc_fb_metrics: needs 4-byte aligned operands");
     const int64_t need = pwc_fb_metrics_workspace_bytes(B, H, W);
     if (workspace_bytes < need || (reinterpret_cast<uintptr_t>(workspace) & 7u))
         PWC_FAIL(PWC_EINVAL, "pwc_fb_metrics: workspace needs %lld bytes, 8-byte aligned", (long long)need);
     Geo g;
-    g.B = B; g.H = H; g.W = W; g.h = h; g.w = w;
+    static_cast<pwc::UpGeo &>(g) = pwc::up_geo_make(H, W, h, w);
+    g.B = B;
     g.tiles_x = (W + kTW - 1) / kTW;
     g.tiles_y = (H + kTH - 1) / kTH;
-    g.same = (h == H && w == W) ? 1 : 0;
-    g.rh = (float)(h - 1) / (float)(H - 1);
-    g.rw = (float)(w - 1) / (float)(W - 1);
-    g.sy = (float)((double)H / (double)h);
-    g.sx = (float)((double)W / (double)w);
     g.bs12 = flow12_bstride;
     g.bs21 = flow21_bstride;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
+    Rec *ws = static_cast<Rec *>(workspace);
     const int64_t nblk = (int64_t)g.tiles_x * g.tiles_y * B;
     hipLaunchKernelGGL(fb_tile_kernel, dim3(g.tiles_x, g.tiles_y, B), dim3(kThreads), 0, st, static_cast<const float *>(flow12),
-                       static_cast<const float *>(flow21), ws + kHead, g);
+                       static_cast<const float *>(flow21), ws + 1, g);
     hipLaunchKernelGGL(fb_finish_kernel, dim3(1), dim3(kThreads), 0, st, ws, nblk, flow21 ? 1 : 0, (double)B * 2 * H * W,
                        (double)B * H * W, static_cast<float *>(out2));
     return pwc::check_launch("fb_tile_kernel");

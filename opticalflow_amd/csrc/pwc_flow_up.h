@@ -7,10 +7,25 @@
 
 namespace pwc {
 
-// (u, v) at full-resolution pixel (Y, X); f = flow of this image ([2][h][w]).  G provides H, W, h, w, same = ((h,w) == (H,W)),
-// rh = (float)(h-1) / (float)(H-1), rw alike, sy = (float)((double)H / h), sx alike.
-template <typename G>
-__device__ __forceinline__ float2 up_flow(const float *f, const G &g, int Y, int X) {
+// geometry of the upsampling: flow [2][h][w] to the image grid H x W; same = ((h,w) == (H,W)), the flow is used as it is
+struct UpGeo {
+    int H, W, h, w, same;
+    float rh, rw, sy, sx;
+};
+
+inline UpGeo up_geo_make(int H, int W, int h, int w) {
+    UpGeo g;
+    g.H = H; g.W = W; g.h = h; g.w = w;
+    g.same = (h == H && w == W) ? 1 : 0;
+    g.rh = (float)(h - 1) / (float)(H - 1);
+    g.rw = (float)(w - 1) / (float)(W - 1);
+    g.sy = (float)((double)H / (double)h);
+    g.sx = (float)((double)W / (double)w);
+    return g;
+}
+
+// (u, v) at full-resolution pixel (Y, X); f = flow of this image ([2][h][w])
+__device__ __forceinline__ float2 up_flow(const float *f, const UpGeo &g, int Y, int X) {
     if (g.same) return make_float2(f[(int64_t)Y * g.W + X], f[(int64_t)g.H * g.W + (int64_t)Y * g.W + X]);
     const float fy = g.rh * (float)Y, fx = g.rw * (float)X;
     const int y0 = (int)fy, x0 = (int)fx;

@@ -11,6 +11,7 @@
 // wave's 64 pixels are 384 contiguous bytes; the three loads share the same cache lines).  Each workgroup leaves {fp64 sum, int64
 // valid, int64 outliers} (fixed tree order) in the workspace; one final workgroup per sample adds that sample's tiles in tile order.
 // No atomics: the result is bit-reproducible.
+#include "pwc_block_reduce.h"
 #include "pwc_common.h"
 #include "pwc_flow_up.h"
 
@@ -19,7 +20,7 @@ namespace {
 constexpr int kTH = 16, kTW = 64, kThreads = 256;
 constexpr int kRowStep = kThreads / kTW;      // 4
 constexpr int kPix = kTH / kRowStep;          // 4 pixels per lane
-constexpr int64_t kRec = 24;                  // {double sum_epe, int64 valid, int64 outliers}
+using Rec = pwc::TilePartial<2>;               // {double sum_epe, int64 {valid, outliers}}: workspace = one per sample, then one per tile
 
 struct Geo {
     pwc::CropUp up;
@@ -27,38 +28,17 @@ struct Geo {
     int64_t bsq;
 };
 
-// fixed-order block sum of one double and two 64-bit counts per lane; result valid in every lane
-__device__ __forceinline__ void block_sum(double &s, long long &nv, long long &no, double *red_s, long long *red_v, long long *red_o) {
-    const int tid = threadIdx.x;
-    red_s[tid] = s;
-    red_v[tid] = nv;
-    red_o[tid] = no;
-    __syncthreads();
-    for (int k = kThreads / 2; k > 0; k >>= 1) {
-        if (tid < k) {
-            red_s[tid] += red_s[tid + k];
-            red_v[tid] += red_v[tid + k];
-            red_o[tid] += red_o[tid + k];
-        }
-        __syncthreads();
-    }
-    s = red_s[0];
-    nv = red_v[0];
-    no = red_o[0];
-}
-
 template <int KIND, bool WRITE>
 __global__ __launch_bounds__(kThreads) void score_tile_kernel(const float *__restrict__ flow_q, const void *__restrict__ gt,
                                                               const uint8_t *__restrict__ valid, float *__restrict__ flow_out,
-                                                              char *__restrict__ part, Geo g) {
-    __shared__ double red_s[kThreads];
-    __shared__ long long red_v[kThreads], red_o[kThreads];
+                                                              Rec *__restrict__ part, Geo g) {
+    __shared__ pwc::TreeLds<kThreads, 1, 2> red;
     const int tid = threadIdx.x, b = blockIdx.z;
     const int col = tid % kTW, row0 = tid / kTW;
     const float *q = flow_q + (int64_t)b * g.bsq;
     const int64_t npix = (int64_t)g.H * g.W;
     double sum = 0.0;
-    long long nv = 0, no = 0;
+    long long cnt[2] = {0, 0};                 // valid, outliers
     const int x = blockIdx.x * kTW + col;
 #pragma unroll
     for (int k = 0; k < kPix; ++k) {
@@ -88,37 +68,32 @@ __global__ __launch_bounds__(kThreads) void score_tile_kernel(const float *__res
         const float epe = sqrtf(du * du + dv * dv);
         const float mag = sqrtf(gu * gu + gv * gv);
         sum += (double)epe;
-        ++nv;
-        if (epe > fmaxf(3.0f, 0.05f * mag)) ++no;
+        ++cnt[0];
+        if (epe > fmaxf(3.0f, 0.05f * mag)) ++cnt[1];
     }
-    block_sum(sum, nv, no, red_s, red_v, red_o);
+    pwc::tree_sum(red, &sum, cnt);
     if (tid == 0) {
         const int64_t lin = blockIdx.x + (int64_t)g.tiles_x * (blockIdx.y + (int64_t)g.tiles_y * blockIdx.z);
-        *reinterpret_cast<double *>(part + lin * kRec) = sum;
-        *reinterpret_cast<long long *>(part + lin * kRec + 8) = nv;
-        *reinterpret_cast<long long *>(part + lin * kRec + 16) = no;
+        part[lin] = Rec{sum, {cnt[0], cnt[1]}};
     }
 }
 
 // workgroup b adds the tiles of sample b in tile order
-__global__ __launch_bounds__(kThreads) void score_finish_kernel(char *__restrict__ ws, int n, int64_t tiles, float *__restrict__ out) {
-    __shared__ double red_s[kThreads];
-    __shared__ long long red_v[kThreads], red_o[kThreads];
+__global__ __launch_bounds__(kThreads) void score_finish_kernel(Rec *__restrict__ ws, int n, int64_t tiles, float *__restrict__ out) {
+    __shared__ pwc::TreeLds<kThreads, 1, 2> red;
     const int tid = threadIdx.x, b = blockIdx.x;
-    const char *part = ws + (int64_t)n * kRec + (int64_t)b * tiles * kRec;
+    const Rec *part = ws + n + (int64_t)b * tiles;
     double s = 0.0;
-    long long nv = 0, no = 0;
+    long long cnt[2] = {0, 0};
     for (int64_t i = tid; i < tiles; i += kThreads) {
-        s += *reinterpret_cast<const double *>(part + i * kRec);
-        nv += *reinterpret_cast<const long long *>(part + i * kRec + 8);
-        no += *reinterpret_cast<const long long *>(part + i * kRec + 16);
+        s += part[i].sum;
+        cnt[0] += part[i].count[0];
+        cnt[1] += part[i].count[1];
     }
-    block_sum(s, nv, no, red_s, red_v, red_o);
+    pwc::tree_sum(red, &s, cnt);
     if (tid == 0) {
-        char *head = ws + (int64_t)b * kRec;
-        *reinterpret_cast<double *>(head) = s;
-        *reinterpret_cast<long long *>(head + 8) = nv;
-        *reinterpret_cast<long long *>(head + 16) = no;
+        ws[b] = Rec{s, {cnt[0], cnt[1]}};
+        const long long nv = cnt[0], no = cnt[1];
         const float nan = __builtin_nanf("");
         out[2 * b] = nv ? (float)(s / (double)nv) : nan;
         out[2 * b + 1] = nv ? (float)(100.0 * (double)no / (double)nv) : nan;
@@ -129,7 +104,7 @@ __global__ __launch_bounds__(kThreads) void score_finish_kernel(char *__restrict
 
 extern "C" int64_t pwc_kitti_score_workspace_bytes(int n, int out_h, int out_w) {
     if (n <= 0 || out_h <= 0 || out_w <= 0) return -1;
-    return kRec * n * (1 + (int64_t)((out_h + kTH - 1) / kTH) * ((out_w + kTW - 1) / kTW));
+    return (int64_t)sizeof(Rec) * n * (1 + (int64_t)((out_h + kTH - 1) / kTH) * ((out_w + kTW - 1) / kTW));
 }
 
 extern "C" int pwc_kitti_score(const void *flow_q, int n, int Hq, int Wq, int crop_h, int crop_w, int out_h, int out_w, int64_t q_bstride,
@@ -148,8 +123,7 @@ extern "C" int pwc_kitti_score(const void *flow_q, int n, int Hq, int Wq, int cr
     const int64_t need = pwc_kitti_score_workspace_bytes(n, out_h, out_w);
     if (workspace_bytes < need) PWC_FAIL(PWC_EINVAL, "pwc_kitti_score: workspace needs %lld bytes, got %lld", (long long)need, (long long)workspace_bytes);
     if (reinterpret_cast<uintptr_t>(workspace) & 7u) PWC_FAIL(PWC_EALIGN, "pwc_kitti_score: workspace must be 8-byte aligned");
-    if (((reinterpret_cast<uintptr_t>(flow_q) | reinterpret_cast<uintptr_t>(flow_out) | reinterpret_cast<uintptr_t>(out)) & 3u) != 0 ||
-        (reinterpret_cast<uintptr_t>(gt) & (gt_kind == 1 ? 1u : 3u)) != 0)
+    if (pwc::misaligned({flow_q, flow_out, out}) || pwc::misaligned({gt}, gt_kind == 1 ? 2 : 4))
         PWC_FAIL(PWC_EALIGN, "pwc_kitti_score: needs 4-byte aligned float operands and a 2-byte aligned uint16 ground truth");
     Geo g;
     g.up = pwc::crop_up_make(Hq, Wq, crop_h, crop_w, out_h, out_w);
@@ -158,12 +132,12 @@ extern "C" int pwc_kitti_score(const void *flow_q, int n, int Hq, int Wq, int cr
     g.tiles_y = (out_h + kTH - 1) / kTH;
     g.bsq = q_bstride;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    char *ws = static_cast<char *>(workspace);
+    Rec *ws = static_cast<Rec *>(workspace);
     const dim3 grid(g.tiles_x, g.tiles_y, n), block(kThreads);
     const float *fq = static_cast<const float *>(flow_q);
     const uint8_t *vd = static_cast<const uint8_t *>(valid);
     float *fo = static_cast<float *>(flow_out);
-    char *part = ws + (int64_t)n * kRec;
+    Rec *part = ws + n;
     if (gt_kind == 1) {
         if (fo) hipLaunchKernelGGL((score_tile_kernel<1, true>), grid, block, 0, st, fq, gt, vd, fo, part, g);
         else hipLaunchKernelGGL((score_tile_kernel<1, false>), grid, block, 0, st, fq, gt, vd, fo, part, g);

@@ -43,6 +43,7 @@
 //             full-resolution pixels whose interpolation uses it, times the vector scale, plus the smoothness term.
 // No atomics on floats: every result is bit-reproducible.  The mask count of the backward is an integer sum (one 64-bit integer
 // atomic per workgroup; integer addition is associative).
+#include "pwc_block_reduce.h"
 #include "pwc_common.h"
 #include "pwc_flow_up.h"
 
@@ -57,26 +58,22 @@ constexpr int kBH = kTH + 4, kBW = kTW + 4;   // backward image window: tile + 2
 constexpr int kBN = kBH * kBW;
 constexpr float kC1 = 1e-4f, kC2 = 9e-4f;     // 0.01^2, 0.03^2 (train_pseudo.py:89, train_fundamental.py:142)
 
-struct Geo {
-    int B, C, H, W, h, w, tiles_x, tiles_y, same;
-    float rh, rw, sy, sx;
+struct Geo : pwc::UpGeo {
+    int B, C, tiles_x, tiles_y;
     int64_t bs_f, bs_1, bs_2, bs_m;
 };
 
 Geo make_geo(int B, int C, int H, int W, int h, int w, int64_t bs_f, int64_t bs_1, int64_t bs_2, int64_t bs_m) {
     Geo g;
-    g.B = B; g.C = C; g.H = H; g.W = W; g.h = h; g.w = w;
+    static_cast<pwc::UpGeo &>(g) = pwc::up_geo_make(H, W, h, w);
+    g.B = B; g.C = C;
     g.tiles_x = (W + kTW - 1) / kTW;
     g.tiles_y = (H + kTH - 1) / kTH;
-    g.same = (h == H && w == W) ? 1 : 0;
-    g.rh = (float)(h - 1) / (float)(H - 1);
-    g.rw = (float)(w - 1) / (float)(W - 1);
-    g.sy = (float)((double)H / (double)h);
-    g.sx = (float)((double)W / (double)w);
     g.bs_f = bs_f; g.bs_1 = bs_1; g.bs_2 = bs_2; g.bs_m = bs_m;
     return g;
 }
 
+using pwc::misaligned;
 using pwc::up_flow;   // pwc_flow_up.h: upsampled flow (u, v) at full-resolution pixel (Y, X)
 
 struct Sample {
@@ -144,9 +141,7 @@ __device__ __forceinline__ float bilinear(const float *p, const Tap &t, int W, f
 }
 
 __device__ __forceinline__ bool mask_on(const void *mask, int mask_u8, int64_t off) {
-    if (!mask) return true;
-    if (mask_u8) return (float)static_cast<const unsigned char *>(mask)[off] > 0.5f;
-    return static_cast<const float *>(mask)[off] > 0.5f;
+    return pwc::mask_val(mask, mask_u8, off) > 0.5f;
 }
 
 // centred 3x3 moments of window arrays xs, ys (row stride ld) around the element at index c
@@ -179,24 +174,6 @@ __device__ __forceinline__ Moments moments(const float *xs, const float *ys, int
     return m;
 }
 
-// fixed-order block sum of n doubles per lane (n <= 4); result valid in lane 0
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double *red) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k) red[k * kThreads + tid] = v[k];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) red[k * kThreads + tid] += red[k * kThreads + tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = red[k * kThreads];
-}
-
 struct FwdArgs {
     const float *flow, *img1, *img2;
     const void *mask;
@@ -209,7 +186,7 @@ struct FwdArgs {
 __global__ __launch_bounds__(kThreads) void proxy_fwd_kernel(FwdArgs a) {
     __shared__ float sx_[kFN], sy_[kFN];
     __shared__ int4 s_tap[kFN];
-    __shared__ double red[4 * kThreads];
+    __shared__ pwc::TreeLds<kThreads, 4> red;
     const Geo &g = a.g;
     const int tid = threadIdx.x, b = blockIdx.z;
     const int Y0 = blockIdx.y * kTH - 1, X0 = blockIdx.x * kTW - 1;
@@ -288,7 +265,7 @@ __global__ __launch_bounds__(kThreads) void proxy_fwd_kernel(FwdArgs a) {
         if (jx < g.w - 1) v[2] += (double)fabsf(fv - fp[q + 1]);
         if (i < g.h - 1) v[3] += (double)fabsf(fv - fp[q + g.w]);
     }
-    block_sum<4>(v, red);
+    pwc::tree_sum(red, v, nullptr);
     if (tid == 0) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) a.part[lin * 4 + k] = v[k];
@@ -297,13 +274,13 @@ __global__ __launch_bounds__(kThreads) void proxy_fwd_kernel(FwdArgs a) {
 
 __global__ __launch_bounds__(kThreads) void proxy_finish_kernel(const double *part, int64_t nblk, int masked, double npix,
                                                                 double nx, double ny, float ap, float as, float *out) {
-    __shared__ double red[4 * kThreads];
+    __shared__ pwc::TreeLds<kThreads, 4> red;
     const int tid = threadIdx.x;
     double v[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t i = tid; i < nblk; i += kThreads)
 #pragma unroll
         for (int k = 0; k < 4; ++k) v[k] += part[i * 4 + k];
-    block_sum<4>(v, red);
+    pwc::tree_sum(red, v, nullptr);
     if (tid == 0) {
         const double den = masked ? (v[1] > 1.0 ? v[1] : 1.0) : npix;
         const float photo = (float)(v[0] / den);
@@ -316,21 +293,16 @@ __global__ __launch_bounds__(kThreads) void proxy_finish_kernel(const double *pa
 
 __global__ __launch_bounds__(kThreads) void mask_count_kernel(const void *mask, int mask_u8, int B, int64_t plane, int64_t bs_m,
                                                               unsigned long long *count) {
-    __shared__ unsigned long long red[kThreads];
+    __shared__ pwc::TreeLds<kThreads, 0, 1> red;
     const int tid = threadIdx.x;
-    unsigned long long n = 0;
+    long long n = 0;
     const int64_t tot = (int64_t)B * plane;
     for (int64_t e = (int64_t)blockIdx.x * kThreads + tid; e < tot; e += (int64_t)gridDim.x * kThreads) {
         const int64_t bb = e / plane;
-        n += mask_on(mask, mask_u8, bb * bs_m + (e - bb * plane)) ? 1ull : 0ull;
+        n += mask_on(mask, mask_u8, bb * bs_m + (e - bb * plane)) ? 1 : 0;
     }
-    red[tid] = n;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0 && red[0]) atomicAdd(count, red[0]);
+    pwc::tree_sum(red, nullptr, &n);
+    if (tid == 0 && n) atomicAdd(count, (unsigned long long)n);
 }
 
 struct BwdArgs {
@@ -569,12 +541,6 @@ int64_t fwd_bytes(int B, int H, int W) {
 }
 int64_t gup_bytes(int B, int H, int W) {
     return ((int64_t)B * 2 * H * W * 4 + 255) / 256 * 256;
-}
-
-bool misaligned(std::initializer_list<const void *> ps) {
-    uintptr_t al = 0;
-    for (const void *p : ps) al |= reinterpret_cast<uintptr_t>(p);
-    return (al & 3u) != 0;
 }
 
 // shared validation of the two loss entries; returns PWC_OK to launch

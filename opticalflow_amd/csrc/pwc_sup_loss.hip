@@ -28,6 +28,7 @@
 //
 // Reductions: per-workgroup fp64 partials in a fixed tree order, then one workgroup adds them in workgroup order.  No float
 // atomics: every result is bit-reproducible.
+#include "pwc_block_reduce.h"
 #include "pwc_common.h"
 
 namespace {
@@ -63,32 +64,10 @@ __device__ __forceinline__ float interp(const float *p, int ld, const Lin &ly, c
     return ly.l0 * (lx.l0 * r0[lx.i0] + lx.l1 * r0[lx.i1]) + ly.l1 * (lx.l0 * r1[lx.i0] + lx.l1 * r1[lx.i1]);
 }
 
-__device__ __forceinline__ float mask_val(const void *mask, int mask_u8, int64_t off) {
-    if (!mask) return 1.0f;
-    if (mask_u8) return (float)static_cast<const unsigned char *>(mask)[off];
-    return static_cast<const float *>(mask)[off];
-}
+using pwc::misaligned;
+using pwc::mask_val;
 
 __device__ __forceinline__ float sgn(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
-
-// fixed-order block sum of N doubles per lane; result in every lane
-template <int N>
-__device__ __forceinline__ void block_sum(double (&v)[N], double *red) {
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int k = 0; k < N; ++k) red[k * kThreads + tid] = v[k];
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {
-        if (tid < s) {
-#pragma unroll
-            for (int k = 0; k < N; ++k) red[k * kThreads + tid] += red[k * kThreads + tid + s];
-        }
-        __syncthreads();
-    }
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = red[k * kThreads];
-    __syncthreads();
-}
 
 // ------------------------------------------------------------------------------------------------ full-resolution loss
 struct FlowArgs {
@@ -129,7 +108,7 @@ __device__ __forceinline__ Up flow_pixel(const FlowArgs &a, int b, int Y, int X)
 }
 
 __global__ __launch_bounds__(kThreads) void flow_fwd_kernel(FlowArgs a) {
-    __shared__ double red[2 * kThreads];
+    __shared__ pwc::TreeLds<kThreads, 2> red;
     const int64_t plane = (int64_t)a.H * a.W, tot = (int64_t)a.B * plane;
     double v[2] = {0.0, 0.0};
 #pragma unroll
@@ -144,7 +123,7 @@ __global__ __launch_bounds__(kThreads) void flow_fwd_kernel(FlowArgs a) {
             v[1] += (double)r.m;
         }
     }
-    block_sum<2>(v, red);
+    pwc::tree_sum(red, v, nullptr);
     if (threadIdx.x == 0) {
         a.part[blockIdx.x * 2] = v[0];
         a.part[blockIdx.x * 2 + 1] = v[1];
@@ -152,13 +131,13 @@ __global__ __launch_bounds__(kThreads) void flow_fwd_kernel(FlowArgs a) {
 }
 
 __global__ __launch_bounds__(kThreads) void flow_finish_kernel(const double *part, int64_t nblk, int masked, int rule, float *out) {
-    __shared__ double red[2 * kThreads];
+    __shared__ pwc::TreeLds<kThreads, 2> red;
     double v[2] = {0.0, 0.0};
     for (int64_t i = threadIdx.x; i < nblk; i += kThreads) {
         v[0] += part[i * 2];
         v[1] += part[i * 2 + 1];
     }
-    block_sum<2>(v, red);
+    pwc::tree_sum(red, v, nullptr);
     if (threadIdx.x == 0) {
         // the mask sum is a float32 sum in the reference; +1e-8 in fp32 as well (rule 1), max(., 1) (rule 0)
         const float s = (float)v[1];
@@ -327,7 +306,7 @@ __device__ __forceinline__ void level_gt(const MsArgs &a, const Level &v, const 
 }
 
 __global__ __launch_bounds__(kThreads) void ms_fwd_kernel(MsArgs a) {
-    __shared__ double red[6 * kThreads];
+    __shared__ pwc::TreeLds<kThreads, 6> red;
     const int l = level_of(a, blockIdx.x);
     const Level &v = a.lv[l];
     const int64_t lp = (int64_t)v.h * v.w;
@@ -364,7 +343,7 @@ __global__ __launch_bounds__(kThreads) void ms_fwd_kernel(MsArgs a) {
             }
         }
     }
-    block_sum<6>(s, red);
+    pwc::tree_sum(red, s, nullptr);
     if (threadIdx.x == 0) {
 #pragma unroll
         for (int k = 0; k < 6; ++k) a.part[blockIdx.x * 6 + k] = s[k];
@@ -372,7 +351,7 @@ __global__ __launch_bounds__(kThreads) void ms_fwd_kernel(MsArgs a) {
 }
 
 __global__ __launch_bounds__(kThreads) void ms_finish_kernel(MsArgs a, float *out) {
-    __shared__ double red[6 * kThreads];
+    __shared__ pwc::TreeLds<kThreads, 6> red;
     double total = 0.0;
     for (int l = 0; l < a.L; ++l) {
         const Level &v = a.lv[l];
@@ -380,7 +359,7 @@ __global__ __launch_bounds__(kThreads) void ms_finish_kernel(MsArgs a, float *ou
         for (int64_t i = threadIdx.x; i < v.nblk; i += kThreads)
 #pragma unroll
             for (int k = 0; k < 6; ++k) s[k] += a.part[(v.blk0 + i) * 6 + k];
-        block_sum<6>(s, red);
+        pwc::tree_sum(red, s, nullptr);
         if (threadIdx.x == 0) {
             const float sc = (float)s[1], sp = (float)s[3];
             const float den_c = sc > 1.0f ? sc : 1.0f;    // valid.sum().clamp(min=1.0)
@@ -466,12 +445,6 @@ __global__ __launch_bounds__(kThreads) void ms_bwd_kernel(MsArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-bool misaligned(std::initializer_list<const void *> ps) {
-    uintptr_t al = 0;
-    for (const void *p : ps) al |= reinterpret_cast<uintptr_t>(p);
-    return (al & 3u) != 0;
-}
-
 int64_t blocks_of(int64_t n) { return (n + kChunk - 1) / kChunk; }
 int64_t align256(int64_t n) { return (n + 255) / 256 * 256; }
 

@@ -16,49 +16,9 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F16, PWC_F32, PwcHipError, check)
-
-_DTYPES = {torch.float32: PWC_F32, torch.float16: PWC_F16}
-
-
-def _dtype_code(t: torch.Tensor) -> int:
-    try:
-        return _DTYPES[t.dtype]
-    except KeyError:
-        raise TypeError("unsupported dtype %s (float32 / float16 only)" % t.dtype) from None
-
-
-def _plane_dense(t: torch.Tensor, name: str) -> int:
-    """Require [B,C,H,W] with dense C,H,W planes; return the batch stride in elements."""
-    if t.dim() != 4:
-        raise ValueError("%s must be 4-D [B,C,H,W], got %s" % (name, tuple(t.shape)))
-    if not t.is_cuda:
-        raise PwcHipError("%s is on %s: the HIP path needs device tensors and has no CPU fallback" % (name, t.device))
-    B, C, H, W = t.shape
-    sb, sc, sh, sw = t.stride()
-    ok = (W == 1 or sw == 1) and (H == 1 or sh == W) and (C == 1 or sc == H * W)
-    if not ok:
-        raise ValueError("%s must have dense C,H,W planes (strides %s for shape %s)" % (name, t.stride(), tuple(t.shape)))
-    if B == 1:
-        return C * H * W
-    if sb < C * H * W:
-        raise ValueError("%s batch stride %d smaller than C*H*W" % (name, sb))
-    return sb
-
-
-def densify(t: torch.Tensor) -> torch.Tensor:
-    """Return t if its C,H,W planes are dense (batch stride free), else a contiguous copy."""
-    if t.dim() == 4:
-        B, C, H, W = t.shape
-        sb, sc, sh, sw = t.stride()
-        if (W == 1 or sw == 1) and (H == 1 or sh == W) and (C == 1 or sc == H * W) and (B == 1 or sb >= C * H * W):
-            return t
-    return t.contiguous()
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
+from ._args import (_bias_arg, _dtype_code, _f32_dense, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr, _query_bytes, _scratch,
+                    _stream, _workspace_args, densify)
+from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F32, PwcHipError, check)
 
 def corr_output_shape(C: int, H: int, W: int, pad_size: int, kernel_size: int, max_displacement: int,
                       stride1: int, stride2: int) -> Tuple[int, int, int]:
@@ -84,10 +44,7 @@ def correlation(in1: torch.Tensor, in2: torch.Tensor, pad_size: int = 4, kernel_
     nch, oh, ow = corr_output_shape(C, H, W, pad_size, kernel_size, max_displacement, stride1, stride2)
     if oh <= 0 or ow <= 0:
         raise ValueError("correlation output would be empty (%d x %d)" % (oh, ow))
-    if out is None:
-        out = torch.empty((B, nch, oh, ow), dtype=in1.dtype, device=in1.device)
-    elif tuple(out.shape) != (B, nch, oh, ow) or out.dtype != in1.dtype or out.device != in1.device:
-        raise ValueError("out must be %s %s on %s" % ((B, nch, oh, ow), in1.dtype, in1.device))
+    out = _out_arg(out, (B, nch, oh, ow), in1.dtype, in1.device)
     bso = _plane_dense(out, "out")
     flags = (FLAG_CORR_NORMALIZE if normalize else 0) | (FLAG_ACT_LEAKY if leaky_slope is not None else 0)
     with torch.cuda.device(in1.device):
@@ -139,10 +96,7 @@ def warp_correlation(in1: torch.Tensor, x2: torch.Tensor, flo: torch.Tensor, flo
     if in1.dtype != torch.float32 or x2.shape != in1.shape or x2.dtype != in1.dtype or tuple(flo.shape) != (B, 2, H, W) \
             or flo.dtype != in1.dtype or x2.device != in1.device or flo.device != in1.device:
         raise ValueError("in1, x2 must be float32 [B,C,H,W] and flo [B,2,H,W] on one device")
-    if out is None:
-        out = torch.empty((B, 81, H, W), dtype=in1.dtype, device=in1.device)
-    elif tuple(out.shape) != (B, 81, H, W) or out.dtype != in1.dtype or out.device != in1.device:
-        raise ValueError("out must be %s" % ((B, 81, H, W),))
+    out = _out_arg(out, (B, 81, H, W), in1.dtype, in1.device)
     bso = _plane_dense(out, "out")
     flags = (FLAG_CORR_NORMALIZE if normalize else 0) | (FLAG_ACT_LEAKY if leaky_slope is not None else 0)
     with torch.cuda.device(in1.device):
@@ -163,10 +117,7 @@ def warp(x: torch.Tensor, flo: torch.Tensor, flow_scale: float = 1.0, align_corn
     B, C, H, W = x.shape
     if tuple(flo.shape) != (B, 2, H, W) or flo.dtype != x.dtype or flo.device != x.device:
         raise ValueError("flo must be %s %s, got %s %s" % ((B, 2, H, W), x.dtype, tuple(flo.shape), flo.dtype))
-    if out is None:
-        out = torch.empty((B, C, H, W), dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != (B, C, H, W) or out.dtype != x.dtype or out.device != x.device:
-        raise ValueError("out must match x")
+    out = _out_arg(out, (B, C, H, W), x.dtype, x.device)
     bso = _plane_dense(out, "out")
     with torch.cuda.device(x.device):
         rc = lib.pwc_warp_fwd(x.data_ptr(), flo.data_ptr(), out.data_ptr(), B, C, H, W,
@@ -192,12 +143,11 @@ def warp_backward(x: torch.Tensor, flo: torch.Tensor, grad_out: torch.Tensor, fl
     gf = torch.empty_like(flo)
     ws, ws_bytes = None, 0
     if deterministic:
-        ws_bytes = lib.pwc_warp_bwd_workspace_bytes(B, C, H, W)
-        ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=x.device)
+        ws, ws_bytes = _scratch(lib.pwc_warp_bwd_workspace_bytes(B, C, H, W), x.device)
     with torch.cuda.device(x.device):
         rc = lib.pwc_warp_bwd(x.data_ptr(), flo.data_ptr(), grad_out.data_ptr(), gx.data_ptr(), gf.data_ptr(),
                               B, C, H, W, float(flow_scale), 1 if align_corners else 0, float(mask_threshold),
-                              _dtype_code(x), ws.data_ptr() if ws is not None else None, ws_bytes, _stream(x))
+                              _dtype_code(x), _ptr(ws), ws_bytes, _stream(x))
     check(rc, "pwc_warp_bwd")
     return gx, gf
 
@@ -230,31 +180,29 @@ def warp_correlation_backward(c1: torch.Tensor, c2: torch.Tensor, flo: Optional[
     bit-reproducible.  Where that entry declines the geometry (PWC_EUNSUPPORTED), or with fused=False, the same gradients come
     from warp_fwd -> mask in torch -> corr_bwd -> warp_bwd (also deterministic; summation order differs)."""
     lib = _lib.load()
-    c1, c2, y, grad_y = densify(c1), densify(c2), densify(y), densify(grad_y)
     B, C, H, W = c1.shape
-    for name, t, shp in (("c1", c1, (B, C, H, W)), ("c2", c2, (B, C, H, W)), ("y", y, (B, 81, H, W)), ("grad_y", grad_y, (B, 81, H, W))) \
-            + ((("flo", flo, (B, 2, H, W)),) if flo is not None else ()):
-        if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != c1.device:
-            raise ValueError("%s must be float32 %s on %s, got %s %s" % (name, shp, c1.device, t.dtype, tuple(t.shape)))
+    dev = c1.device
+    c1, bs1 = _f32_dense(c1, "c1", (B, C, H, W), dev)
+    c2, bs2 = _f32_dense(c2, "c2", (B, C, H, W), dev)
+    y, bsy = _f32_dense(y, "y", (B, 81, H, W), dev)
+    grad_y, bsg = _f32_dense(grad_y, "grad_y", (B, 81, H, W), dev)
+    bsf = 0
     if flo is not None:
-        flo = densify(flo)
+        flo, bsf = _f32_dense(flo, "flo", (B, 2, H, W), dev)
     if fused:
-        bs = [_plane_dense(t, n) for t, n in ((c1, "c1"), (c2, "c2"), (y, "y"), (grad_y, "grad_y"))]
-        bsf = _plane_dense(flo, "flo") if flo is not None else 0
         g1 = torch.empty((B, C, H, W), dtype=torch.float32, device=c1.device)
         g2 = torch.empty_like(g1)
         gf = torch.empty((B, 2, H, W), dtype=torch.float32, device=c1.device) if flo is not None else None
         ws, ws_bytes = None, 0
         if flo is not None:
-            ws_bytes = lib.pwc_warp_corr81_bwd_workspace_bytes(B, C, H, W)
-            ws = torch.empty((ws_bytes + 7) // 8, dtype=torch.int64, device=c1.device)
+            ws, ws_bytes = _scratch(lib.pwc_warp_corr81_bwd_workspace_bytes(B, C, H, W), c1.device)
         flags = (FLAG_CORR_NORMALIZE if normalize else 0) | (FLAG_ACT_LEAKY if leaky_slope is not None else 0)
         with torch.cuda.device(c1.device):
-            rc = lib.pwc_warp_corr81_bwd(c1.data_ptr(), c2.data_ptr(), flo.data_ptr() if flo is not None else None, y.data_ptr(),
-                                         grad_y.data_ptr(), g1.data_ptr(), g2.data_ptr(), gf.data_ptr() if gf is not None else None,
+            rc = lib.pwc_warp_corr81_bwd(c1.data_ptr(), c2.data_ptr(), _ptr(flo), y.data_ptr(),
+                                         grad_y.data_ptr(), g1.data_ptr(), g2.data_ptr(), _ptr(gf),
                                          B, C, H, W, float(flow_scale), 1 if align_corners else 0, float(mask_threshold),
-                                         float(corr_multiply), flags, float(leaky_slope or 0.0), bs[0], bs[1], bsf, bs[2], bs[3],
-                                         ws.data_ptr() if ws is not None else None, ws_bytes, _stream(c1))
+                                         float(corr_multiply), flags, float(leaky_slope or 0.0), bs1, bs2, bsf, bsy, bsg,
+                                         _ptr(ws), ws_bytes, _stream(c1))
         if rc != -2:                               # PWC_EUNSUPPORTED: take the composition below
             check(rc, "pwc_warp_corr81_bwd")
             return g1, g2, gf
@@ -331,16 +279,10 @@ def conv3x3(x: torch.Tensor, wpacked: torch.Tensor, bias: torch.Tensor, cout: in
     bsx = _plane_dense(x, "x")
     B, cin, H, W = x.shape
     ho, wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    if out is None:
-        out = torch.empty((B, cout, ho, wo), dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != (B, cout, ho, wo) or out.dtype != x.dtype or out.device != x.device:
-        raise ValueError("out must be %s, got %s" % ((B, cout, ho, wo), tuple(out.shape)))
+    out = _out_arg(out, (B, cout, ho, wo), x.dtype, x.device)
     bsy = _plane_dense(out, "out")
-    need = lib.pwc_conv3x3_packed_bytes(cin, cout, PWC_F32)
-    if wpacked.dtype != torch.float32 or wpacked.numel() * 4 != need or wpacked.device != x.device:
-        raise ValueError("packed weights do not match Cin=%d Cout=%d (have %d B, need %d B)" % (cin, cout, wpacked.numel() * 4, need))
-    if bias.dtype != torch.float32 or bias.numel() != cout or bias.device != x.device or not bias.is_contiguous():
-        raise ValueError("bias must be float32[%d] on %s" % (cout, x.device))
+    _packed_arg(wpacked, lib.pwc_conv3x3_packed_bytes(cin, cout, PWC_F32), x.device, "weights")
+    _bias_arg(bias, cout, x.device)
     flags = FLAG_ACT_LEAKY if leaky_slope is not None else 0
     res_ptr, bsr = 0, 0
     if residual is not None:
@@ -349,11 +291,7 @@ def conv3x3(x: torch.Tensor, wpacked: torch.Tensor, bias: torch.Tensor, cout: in
         bsr = _plane_dense(residual, "residual")
         res_ptr = residual.data_ptr()
         flags |= FLAG_CONV_RESIDUAL
-    ws_ptr, ws_bytes = 0, 0
-    if workspace is not None:
-        if workspace.device != x.device or not workspace.is_contiguous():
-            raise ValueError("workspace must be a contiguous tensor on %s" % x.device)
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    ws_ptr, ws_bytes = _workspace_args(workspace, x)
     with torch.cuda.device(x.device):
         rc = lib.pwc_conv2d_fwd(x.data_ptr(), wpacked.data_ptr(), bias.data_ptr(), res_ptr, out.data_ptr(),
                                 B, cin, H, W, cout, stride, dilation, _dtype_code(x), flags,
@@ -385,10 +323,7 @@ def pack_conv3x3_wino(weight: torch.Tensor) -> torch.Tensor:
 
 def conv3x3_wino_workspace_bytes(B: int, cin: int, H: int, W: int, cout: int, dilation: int = 1) -> int:
     """Scratch bytes the split-K form of this layer wants (0 = it does not split)."""
-    n = _lib.load().pwc_conv3x3_wino_workspace_bytes(B, cin, H, W, cout, dilation)
-    if n < 0:
-        raise ValueError("bad conv geometry")
-    return int(n)
+    return _query_bytes(_lib.load().pwc_conv3x3_wino_workspace_bytes(B, cin, H, W, cout, dilation), "conv")
 
 
 def conv3x3_wino(x: torch.Tensor, upacked: torch.Tensor, bias: torch.Tensor, cout: int, leaky_slope: Optional[float] = 0.1,
@@ -399,21 +334,11 @@ def conv3x3_wino(x: torch.Tensor, upacked: torch.Tensor, bias: torch.Tensor, cou
     B, cin, H, W = x.shape
     if x.dtype != torch.float32:
         raise ValueError("conv3x3_wino is fp32 only")
-    if out is None:
-        out = torch.empty((B, cout, H, W), dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != (B, cout, H, W) or out.dtype != x.dtype or out.device != x.device:
-        raise ValueError("out must be %s, got %s" % ((B, cout, H, W), tuple(out.shape)))
+    out = _out_arg(out, (B, cout, H, W), x.dtype, x.device)
     bsy = _plane_dense(out, "out")
-    need = lib.pwc_conv3x3_wino_packed_bytes(cin, cout)
-    if upacked.dtype != torch.float32 or upacked.numel() * 4 != need or upacked.device != x.device:
-        raise ValueError("packed Winograd filters do not match Cin=%d Cout=%d (have %d B, need %d B)" % (cin, cout, upacked.numel() * 4, need))
-    if bias.dtype != torch.float32 or bias.numel() != cout or bias.device != x.device or not bias.is_contiguous():
-        raise ValueError("bias must be float32[%d] on %s" % (cout, x.device))
-    ws_ptr, ws_bytes = 0, 0
-    if workspace is not None:
-        if workspace.device != x.device or not workspace.is_contiguous():
-            raise ValueError("workspace must be a contiguous tensor on %s" % x.device)
-        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    _packed_arg(upacked, lib.pwc_conv3x3_wino_packed_bytes(cin, cout), x.device, "Winograd filters")
+    _bias_arg(bias, cout, x.device)
+    ws_ptr, ws_bytes = _workspace_args(workspace, x)
     with torch.cuda.device(x.device):
         rc = lib.pwc_conv3x3_wino_fwd(x.data_ptr(), upacked.data_ptr(), bias.data_ptr(), out.data_ptr(), B, cin, H, W, cout, dilation,
                                       FLAG_ACT_LEAKY if leaky_slope is not None else 0, float(leaky_slope or 0.0), bsx, bsy,
@@ -451,15 +376,10 @@ def pyr1_wino(x: torch.Tensor, upacked: torch.Tensor, bias: torch.Tensor, leaky_
     B, cin, H, W = x.shape
     if x.dtype != torch.float32 or cin != 16:
         raise ValueError("pyr1_wino takes float32 [B,16,H,W], got %s %s" % (x.dtype, tuple(x.shape)))
-    if out is None:
-        out = torch.empty((B, 16, H, W), dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != (B, 16, H, W) or out.dtype != x.dtype or out.device != x.device:
-        raise ValueError("out must be %s, got %s" % ((B, 16, H, W), tuple(out.shape)))
+    out = _out_arg(out, (B, 16, H, W), x.dtype, x.device)
     bsy = _plane_dense(out, "out")
-    if upacked.dtype != torch.float32 or upacked.numel() * 4 != lib.pwc_pyr1_wino_packed_bytes() or upacked.device != x.device:
-        raise ValueError("packed filters are not those of pack_pyr1_wino")
-    if bias.dtype != torch.float32 or bias.numel() != 16 or bias.device != x.device or not bias.is_contiguous():
-        raise ValueError("bias must be float32[16] on %s" % x.device)
+    _packed_arg(upacked, lib.pwc_pyr1_wino_packed_bytes(), x.device, "pack_pyr1_wino filters")
+    _bias_arg(bias, 16, x.device)
     with torch.cuda.device(x.device):
         rc = lib.pwc_pyr1_wino_fwd(x.data_ptr(), upacked.data_ptr(), bias.data_ptr(), out.data_ptr(), B, H, W, float(leaky_slope),
                                    bsx, bsy, _stream(x))
@@ -475,17 +395,12 @@ def pyr1_wino_pair(x: torch.Tensor, upacked1: torch.Tensor, bias1: torch.Tensor,
     B, cin, H, W = x.shape
     if x.dtype != torch.float32 or cin != 16:
         raise ValueError("pyr1_wino_pair takes float32 [B,16,H,W], got %s %s" % (x.dtype, tuple(x.shape)))
-    if out is None:
-        out = torch.empty((B, 16, H, W), dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != (B, 16, H, W) or out.dtype != x.dtype or out.device != x.device:
-        raise ValueError("out must be %s, got %s" % ((B, 16, H, W), tuple(out.shape)))
+    out = _out_arg(out, (B, 16, H, W), x.dtype, x.device)
     bsy = _plane_dense(out, "out")
     need = lib.pwc_pyr1_wino_packed_bytes()
     for up, bias in ((upacked1, bias1), (upacked2, bias2)):
-        if up.dtype != torch.float32 or up.numel() * 4 != need or up.device != x.device:
-            raise ValueError("packed filters are not those of pack_pyr1_wino")
-        if bias.dtype != torch.float32 or bias.numel() != 16 or bias.device != x.device or not bias.is_contiguous():
-            raise ValueError("bias must be float32[16] on %s" % x.device)
+        _packed_arg(up, need, x.device, "pack_pyr1_wino filters")
+        _bias_arg(bias, 16, x.device)
     with torch.cuda.device(x.device):
         rc = lib.pwc_pyr1_wino_pair_fwd(x.data_ptr(), upacked1.data_ptr(), bias1.data_ptr(), upacked2.data_ptr(), bias2.data_ptr(),
                                         out.data_ptr(), B, H, W, float(leaky_slope), bsx, bsy, _stream(x))
@@ -514,20 +429,9 @@ def pack_conv3x3_wino4(weight: torch.Tensor) -> torch.Tensor:
     return up
 
 
-def _workspace_args(workspace: Optional[torch.Tensor], x: torch.Tensor) -> Tuple[int, int]:
-    if workspace is None:
-        return 0, 0
-    if workspace.device != x.device or not workspace.is_contiguous():
-        raise ValueError("workspace must be a contiguous tensor on %s" % x.device)
-    return workspace.data_ptr(), workspace.numel() * workspace.element_size()
-
-
 def conv3x3_wino4_workspace_bytes(B: int, cin: int, H: int, W: int, cout: int) -> int:
     """Scratch bytes the tail split of this layer's F(4x4) launches wants (0 = no partial last round worth splitting)."""
-    n = _lib.load().pwc_conv3x3_wino4_workspace_bytes(B, cin, H, W, cout)
-    if n < 0:
-        raise ValueError("bad conv geometry")
-    return int(n)
+    return _query_bytes(_lib.load().pwc_conv3x3_wino4_workspace_bytes(B, cin, H, W, cout), "conv")
 
 
 def conv3x3_wino4(x: torch.Tensor, upacked: torch.Tensor, bias: torch.Tensor, cout: int, leaky_slope: Optional[float] = 0.1,
@@ -545,16 +449,10 @@ def conv3x3_wino4(x: torch.Tensor, upacked: torch.Tensor, bias: torch.Tensor, co
     oshape = (4 * B, cout, H // 2, W // 2) if split2 else (B, cout, H, W)
     if split2 and (H % 2 or W % 8):
         raise ValueError("split2 needs even H and W % 8 == 0")
-    if out is None:
-        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != oshape or out.dtype != x.dtype or out.device != x.device:
-        raise ValueError("out must be %s, got %s" % (oshape, tuple(out.shape)))
+    out = _out_arg(out, oshape, x.dtype, x.device)
     bsy = _plane_dense(out, "out")
-    need = lib.pwc_conv3x3_wino4_packed_bytes(cin, cout)
-    if upacked.dtype != torch.float32 or upacked.numel() * 4 != need or upacked.device != x.device:
-        raise ValueError("packed F(4x4,3x3) filters do not match Cin=%d Cout=%d (have %d B, need %d B)" % (cin, cout, upacked.numel() * 4, need))
-    if bias.dtype != torch.float32 or bias.numel() != cout or bias.device != x.device or not bias.is_contiguous():
-        raise ValueError("bias must be float32[%d] on %s" % (cout, x.device))
+    _packed_arg(upacked, lib.pwc_conv3x3_wino4_packed_bytes(cin, cout), x.device, "F(4x4,3x3) filters")
+    _bias_arg(bias, cout, x.device)
     ws_ptr, ws_bytes = _workspace_args(workspace, x)
     with torch.cuda.device(x.device):
         rc = lib.pwc_conv3x3_wino4_fwd(x.data_ptr(), upacked.data_ptr(), bias.data_ptr(), out.data_ptr(), B, cin, H, W, cout, 1,
@@ -568,16 +466,12 @@ def kitti_ingest(pairs_u8: torch.Tensor, mean, std, out: Optional[torch.Tensor] 
     """uint8 RGB pairs [n,2,H,W,3] on the device -> float32 [n,6,Hp,Wp] (Hp, Wp = H, W rounded up to multiples of 64): ToTensor +
     (v - mean) / std per channel, the two images concatenated along the channels, replicate padding (inference_kitti.py:53-63,175-178,
     208-210) as one kernel (C-ABI pwc_kitti_ingest_u8)."""
-    import ctypes
     if not pairs_u8.is_cuda or pairs_u8.dtype != torch.uint8 or pairs_u8.dim() != 5 or pairs_u8.shape[1] != 2 or pairs_u8.shape[4] != 3 \
             or not pairs_u8.is_contiguous():
         raise ValueError("pairs_u8 must be a contiguous uint8 device tensor [n,2,H,W,3]")
     n, _, H, W, _ = pairs_u8.shape
     Hp, Wp = (H + 63) // 64 * 64, (W + 63) // 64 * 64
-    if out is None:
-        out = torch.empty((n, 6, Hp, Wp), dtype=torch.float32, device=pairs_u8.device)
-    elif tuple(out.shape) != (n, 6, Hp, Wp) or out.dtype != torch.float32 or out.device != pairs_u8.device:
-        raise ValueError("out must be float32 %s" % ((n, 6, Hp, Wp),))
+    out = _out_arg(out, (n, 6, Hp, Wp), torch.float32, pairs_u8.device)
     bso = _plane_dense(out, "out")
     m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
     s3 = (ctypes.c_float * 3)(*[float(v) for v in std])
@@ -594,10 +488,7 @@ def flow_upsample(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, ou
         raise ValueError("flow_q must be a float32 device tensor [n,2,Hq,Wq]")
     n, _, Hq, Wq = flow_q.shape
     bsq = _plane_dense(flow_q, "flow_q")
-    if out is None:
-        out = torch.empty((n, 2, out_h, out_w), dtype=torch.float32, device=flow_q.device)
-    elif tuple(out.shape) != (n, 2, out_h, out_w) or out.dtype != torch.float32 or out.device != flow_q.device or not out.is_contiguous():
-        raise ValueError("out must be contiguous float32 %s" % ((n, 2, out_h, out_w),))
+    out = _out_arg(out, (n, 2, out_h, out_w), torch.float32, flow_q.device, contiguous=True)
     with torch.cuda.device(flow_q.device):
         rc = _lib.load().pwc_flow_upsample_f32(flow_q.data_ptr(), out.data_ptr(), n, Hq, Wq, crop_h, crop_w, out_h, out_w, bsq, _stream(flow_q))
     check(rc, "pwc_flow_upsample_f32")
@@ -605,10 +496,7 @@ def flow_upsample(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, ou
 
 
 def kitti_score_workspace_bytes(n: int, out_h: int, out_w: int) -> int:
-    nb = _lib.load().pwc_kitti_score_workspace_bytes(n, out_h, out_w)
-    if nb < 0:
-        raise ValueError("bad kitti-score geometry")
-    return int(nb)
+    return _query_bytes(_lib.load().pwc_kitti_score_workspace_bytes(n, out_h, out_w), "kitti-score")
 
 
 _SCORE_WS = {}
@@ -650,10 +538,7 @@ def kitti_score(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, out_
     if flow_out is not None and (tuple(flow_out.shape) != (n, 2, out_h, out_w) or flow_out.dtype != torch.float32 or flow_out.device != dev
                                  or not flow_out.is_contiguous()):
         raise ValueError("flow_out must be contiguous float32 %s on %s" % ((n, 2, out_h, out_w), dev))
-    if out is None:
-        out = torch.empty((n, 2), dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (n, 2) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float32 %s tensor on %s" % ((n, 2), dev))
+    out = _out_arg(out, (n, 2), torch.float32, dev, contiguous=True)
     with torch.cuda.device(dev):
         nb = kitti_score_workspace_bytes(max(n, 1), max(out_h, 1), max(out_w, 1))
         key = (dev, n, out_h, out_w)
@@ -661,8 +546,7 @@ def kitti_score(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, out_
         if ws is None:
             ws = _SCORE_WS[key] = torch.empty(nb // 8, dtype=torch.int64, device=dev)
         rc = _lib.load().pwc_kitti_score(flow_q.data_ptr(), n, Hq, Wq, int(crop_h), int(crop_w), out_h, out_w, bsq, gt.data_ptr(), kind,
-                                         valid.data_ptr() if valid is not None else None,
-                                         flow_out.data_ptr() if flow_out is not None else None, ws.data_ptr(), nb, out.data_ptr(),
+                                         _ptr(valid), _ptr(flow_out), ws.data_ptr(), nb, out.data_ptr(),
                                          _stream(flow_q))
     check(rc, "pwc_kitti_score")
     if raw:
@@ -677,10 +561,7 @@ def lattice_unsplit(x: torch.Tensor, batch: int, levels: int, out: Optional[torc
         raise ValueError("x must be a contiguous float32 device tensor [batch * 4**levels, C, h, w]")
     _, C, h, w = x.shape
     oshape = (batch, C, h << levels, w << levels)
-    if out is None:
-        out = torch.empty(oshape, dtype=x.dtype, device=x.device)
-    elif tuple(out.shape) != oshape or out.dtype != x.dtype or out.device != x.device:
-        raise ValueError("out must be %s, got %s" % (oshape, tuple(out.shape)))
+    out = _out_arg(out, oshape, x.dtype, x.device)
     bsy = _plane_dense(out, "out")
     with torch.cuda.device(x.device):
         rc = _lib.load().pwc_lattice_unsplit_f32(x.data_ptr(), out.data_ptr(), batch, C, h, w, levels, bsy, _stream(x))
@@ -690,10 +571,7 @@ def lattice_unsplit(x: torch.Tensor, batch: int, levels: int, out: Optional[torc
 
 def conv3x3_workspace_bytes(B: int, cin: int, H: int, W: int, cout: int, stride: int = 1, dilation: int = 1) -> int:
     """Scratch bytes the split-K route of this layer wants (0 = it never splits)."""
-    n = _lib.load().pwc_conv2d_workspace_bytes(B, cin, H, W, cout, stride, dilation)
-    if n < 0:
-        raise ValueError("bad conv geometry")
-    return int(n)
+    return _query_bytes(_lib.load().pwc_conv2d_workspace_bytes(B, cin, H, W, cout, stride, dilation), "conv")
 
 
 def head_upfeat_supported(B: int, H: int, W: int, min_tiles: int = 64) -> bool:
@@ -705,10 +583,7 @@ def head_upfeat_supported(B: int, H: int, W: int, min_tiles: int = 64) -> bool:
 
 def head_upfeat_workspace_bytes(B: int, cin: int, H: int, W: int) -> int:
     """Scratch bytes pwc_head_upfeat_ws_fwd wants for this geometry (Cin slices of launches smaller than the chip; 0 = never)."""
-    n = _lib.load().pwc_head_upfeat_workspace_bytes(B, cin, H, W)
-    if n < 0:
-        raise ValueError("bad head geometry")
-    return int(n)
+    return _query_bytes(_lib.load().pwc_head_upfeat_workspace_bytes(B, cin, H, W), "head")
 
 
 def head_upfeat(x: torch.Tensor, head_wpacked: torch.Tensor, head_bias: torch.Tensor, up_weight: torch.Tensor,
@@ -805,49 +680,22 @@ def proxy_loss_workspace_bytes(B: int, C: int, H: int, W: int, h: int, w: int, f
     """Scratch bytes of pwc_proxy_loss_bwd (enough for the forward too), or of pwc_proxy_loss_fwd alone with forward_only."""
     lib = _lib.load()
     fn = lib.pwc_proxy_loss_fwd_workspace_bytes if forward_only else lib.pwc_proxy_loss_workspace_bytes
-    n = fn(B, C, H, W, h, w)
-    if n < 0:
-        raise ValueError("bad proxy-loss geometry")
-    return int(n)
-
-
-def _mask_arg(mask: Optional[torch.Tensor], B: int, H: int, W: int) -> Tuple[Optional[torch.Tensor], int, int]:
-    """[B,H,W] / [B,1,H,W] mask as the kernels read it: (tensor, mask_u8, batch stride).  bool -> its bytes; float32 as is;
-    any other dtype -> (mask > 0.5) as bytes (the same decision the kernels take on f32)."""
-    if mask is None:
-        return None, 0, 0
-    if mask.dim() == 4:
-        mask = mask[:, 0]
-    if tuple(mask.shape) != (B, H, W):
-        raise ValueError("valid_mask must be [B,H,W] or [B,1,H,W] = %s, got %s" % ((B, H, W), tuple(mask.shape)))
-    if mask.dtype == torch.bool:
-        m, u8 = mask.contiguous().view(torch.uint8), 1
-    elif mask.dtype == torch.float32:
-        m, u8 = mask.contiguous(), 0
-    elif mask.dtype == torch.uint8:
-        m, u8 = mask.contiguous(), 1
-    else:
-        m, u8 = (mask > 0.5).contiguous().view(torch.uint8), 1
-    return m, u8, H * W
+    return _query_bytes(fn(B, C, H, W, h, w), "proxy-loss")
 
 
 def _proxy_args(flow, img1, img2, mask):
-    flow, img1, img2 = densify(flow), densify(img1), densify(img2)
     B, C, H, W = img1.shape
     h, w = flow.shape[-2:]
-    for name, t, shp in (("flow", flow, (B, 2, h, w)), ("img1", img1, (B, C, H, W)), ("img2", img2, (B, C, H, W))):
-        if tuple(t.shape) != shp or t.dtype != torch.float32 or t.device != img1.device:
-            raise ValueError("%s must be float32 %s on %s, got %s %s" % (name, shp, img1.device, t.dtype, tuple(t.shape)))
-    m, u8, bsm = _mask_arg(mask, B, H, W)
-    if m is not None and m.device != img1.device:
-        raise ValueError("valid_mask must be on %s" % img1.device)
-    bs = (_plane_dense(flow, "flow"), _plane_dense(img1, "img1"), _plane_dense(img2, "img2"))
-    return flow, img1, img2, m, u8, bsm, bs, (B, C, H, W, h, w)
+    dev = img1.device
+    flow, bsf = _f32_dense(flow, "flow", (B, 2, h, w), dev)
+    img1, bs1 = _f32_dense(img1, "img1", (B, C, H, W), dev)
+    img2, bs2 = _f32_dense(img2, "img2", (B, C, H, W), dev)
+    m, u8, bsm = _mask_arg(mask, B, H, W, dev, "threshold", "valid_mask")
+    return flow, img1, img2, m, u8, bsm, (bsf, bs1, bs2), (B, C, H, W, h, w)
 
 
 def _proxy_workspace(dims, device, forward_only=False) -> Tuple[torch.Tensor, int]:
-    nb = proxy_loss_workspace_bytes(*dims, forward_only=forward_only)
-    return torch.empty((nb + 7) // 8, dtype=torch.int64, device=device), nb
+    return _scratch(proxy_loss_workspace_bytes(*dims, forward_only=forward_only), device)
 
 
 def proxy_loss(flow: torch.Tensor, img1: torch.Tensor, img2: torch.Tensor, mask: Optional[torch.Tensor] = None,
@@ -859,7 +707,7 @@ def proxy_loss(flow: torch.Tensor, img1: torch.Tensor, img2: torch.Tensor, mask:
     out = torch.empty(3, dtype=torch.float32, device=img1.device)
     with torch.cuda.device(img1.device):
         ws, nb = _proxy_workspace(dims, img1.device, forward_only=True)
-        rc = lib.pwc_proxy_loss_fwd(flow.data_ptr(), img1.data_ptr(), img2.data_ptr(), m.data_ptr() if m is not None else None, u8,
+        rc = lib.pwc_proxy_loss_fwd(flow.data_ptr(), img1.data_ptr(), img2.data_ptr(), _ptr(m), u8,
                                     out.data_ptr(), *dims, float(alpha_photo), float(alpha_smooth), float(ssim_eps),
                                     bs[0], bs[1], bs[2], bsm, ws.data_ptr(), nb, _stream(img1))
     check(rc, "pwc_proxy_loss_fwd")
@@ -878,7 +726,7 @@ def proxy_loss_backward(flow: torch.Tensor, img1: torch.Tensor, img2: torch.Tens
     gf = torch.empty((B, 2, h, w), dtype=torch.float32, device=img1.device)
     with torch.cuda.device(img1.device):
         ws, nb = _proxy_workspace(dims, img1.device)
-        rc = lib.pwc_proxy_loss_bwd(flow.data_ptr(), img1.data_ptr(), img2.data_ptr(), m.data_ptr() if m is not None else None, u8,
+        rc = lib.pwc_proxy_loss_bwd(flow.data_ptr(), img1.data_ptr(), img2.data_ptr(), _ptr(m), u8,
                                     g.data_ptr(), gf.data_ptr(), *dims, float(alpha_photo), float(alpha_smooth), float(ssim_eps),
                                     bs[0], bs[1], bs[2], bsm, ws.data_ptr(), nb, _stream(img1))
     check(rc, "pwc_proxy_loss_bwd")
@@ -938,10 +786,7 @@ def fb_metrics_supported(flow12: torch.Tensor, flow21: Optional[torch.Tensor], H
 
 
 def fb_metrics_workspace_bytes(B: int, H: int, W: int) -> int:
-    n = _lib.load().pwc_fb_metrics_workspace_bytes(B, H, W)
-    if n < 0:
-        raise ValueError("bad fb-metrics geometry")
-    return int(n)
+    return _query_bytes(_lib.load().pwc_fb_metrics_workspace_bytes(B, H, W), "fb-metrics")
 
 
 def fb_metrics(flow12: torch.Tensor, flow21: Optional[torch.Tensor], H: int, W: int, out: Optional[torch.Tensor] = None,
@@ -952,27 +797,17 @@ def fb_metrics(flow12: torch.Tensor, flow21: Optional[torch.Tensor], H: int, W: 
     One launch pair, no host synchronisation, bit-reproducible.  raw=True returns (out, cycle_sum, oob_count): the float64 sum
     and the int64 count the two ratios were formed from, as 0-dim device tensors."""
     lib = _lib.load()
-    flow12 = densify(flow12)
     B, _, h, w = flow12.shape
     dev = flow12.device
-    flows = [("flow12", flow12)]
+    flow12, bs12 = _f32_dense(flow12, "flow12", (B, 2, h, w), dev)
+    bs21 = 0
     if flow21 is not None:
-        flow21 = densify(flow21)
-        flows.append(("flow21", flow21))
-    for name, t in flows:
-        if tuple(t.shape) != (B, 2, h, w) or t.dtype != torch.float32 or t.device != dev:
-            raise ValueError("%s must be float32 %s on %s, got %s %s" % (name, (B, 2, h, w), dev, t.dtype, tuple(t.shape)))
-    bs12 = _plane_dense(flow12, "flow12")
-    bs21 = _plane_dense(flow21, "flow21") if flow21 is not None else 0
-    if out is None:
-        out = torch.empty(2, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != (2,) or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-        raise ValueError("out must be a contiguous float32 [2] tensor on %s" % dev)
+        flow21, bs21 = _f32_dense(flow21, "flow21", (B, 2, h, w), dev)
+    out = _out_arg(out, (2,), torch.float32, dev, contiguous=True)
     H, W = int(H), int(W)
     with torch.cuda.device(dev):
-        nb = fb_metrics_workspace_bytes(B, max(H, 1), max(W, 1))
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
-        rc = lib.pwc_fb_metrics(flow12.data_ptr(), flow21.data_ptr() if flow21 is not None else None, B, h, w, H, W, bs12, bs21,
+        ws, nb = _scratch(fb_metrics_workspace_bytes(B, max(H, 1), max(W, 1)), dev)
+        rc = lib.pwc_fb_metrics(flow12.data_ptr(), _ptr(flow21), B, h, w, H, W, bs12, bs21,
                                 ws.data_ptr(), nb, out.data_ptr(), _stream(flow12))
     check(rc, "pwc_fb_metrics")
     if raw:
@@ -1022,36 +857,8 @@ def sup_multiscale_loss_supported(preds, gt: torch.Tensor, mask: Optional[torch.
     return 6 * H * W < 2 ** 31 and 1 <= B <= 65535
 
 
-def _sup_mask(mask: Optional[torch.Tensor], B: int, H: int, W: int) -> Tuple[Optional[torch.Tensor], int, int]:
-    """[B,H,W] / [B,1,H,W] mask as the kernels read it, raw values kept: (tensor, mask_u8, batch stride).  bool / uint8 -> bytes,
-    float32 as is, any other dtype -> float32."""
-    if mask is None:
-        return None, 0, 0
-    if mask.dim() == 4:
-        mask = mask[:, 0]
-    if tuple(mask.shape) != (B, H, W):
-        raise ValueError("mask must be [B,H,W] or [B,1,H,W] = %s, got %s" % ((B, H, W), tuple(mask.shape)))
-    if mask.dtype == torch.bool:
-        m, u8 = mask.contiguous().view(torch.uint8), 1
-    elif mask.dtype == torch.uint8:
-        m, u8 = mask.contiguous(), 1
-    else:
-        m, u8 = mask.contiguous().float(), 0
-    return m, u8, H * W
-
-
-def _f32_dense(t: torch.Tensor, name: str, shape, device) -> Tuple[torch.Tensor, int]:
-    t = densify(t)
-    if tuple(t.shape) != tuple(shape) or t.dtype != torch.float32 or t.device != device:
-        raise ValueError("%s must be float32 %s on %s, got %s %s on %s" % (name, tuple(shape), device, t.dtype, tuple(t.shape), t.device))
-    return t, _plane_dense(t, name)
-
-
 def sup_flow_loss_workspace_bytes(B: int, H: int, W: int, h: int, w: int, backward: bool = False) -> int:
-    n = _lib.load().pwc_sup_flow_loss_workspace_bytes(B, H, W, h, w, 1 if backward else 0)
-    if n < 0:
-        raise ValueError("bad flow-loss geometry")
-    return int(n)
+    return _query_bytes(_lib.load().pwc_sup_flow_loss_workspace_bytes(B, H, W, h, w, 1 if backward else 0), "flow-loss")
 
 
 def _sup_flow_args(pred, gt, mask):
@@ -1065,9 +872,7 @@ def _sup_flow_args(pred, gt, mask):
     h, w = pred.shape[-2:]
     gt, bsg = _f32_dense(gt, "gt", (B, 2, H, W), gt.device)
     pred, bsp = _f32_dense(pred, "pred", (B, 2, h, w), gt.device)
-    m, u8, bsm = _sup_mask(mask, B, H, W)
-    if m is not None and m.device != gt.device:
-        raise ValueError("mask must be on %s" % gt.device)
+    m, u8, bsm = _mask_arg(mask, B, H, W, gt.device, "raw")
     return pred, gt, m, u8, (B, H, W, h, w), (bsp, bsg, bsm)
 
 
@@ -1080,9 +885,8 @@ def sup_flow_loss(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[torch.Ten
     pred, gt, m, u8, dims, bs = _sup_flow_args(pred, gt, mask)
     out = torch.empty(2, dtype=torch.float32, device=gt.device)
     with torch.cuda.device(gt.device):
-        nb = sup_flow_loss_workspace_bytes(*dims)
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
-        rc = lib.pwc_sup_flow_loss_fwd(pred.data_ptr(), gt.data_ptr(), m.data_ptr() if m is not None else None, u8,
+        ws, nb = _scratch(sup_flow_loss_workspace_bytes(*dims), gt.device)
+        rc = lib.pwc_sup_flow_loss_fwd(pred.data_ptr(), gt.data_ptr(), _ptr(m), u8,
                                        MASK_RULES[rule], out.data_ptr(), *dims, float(eps), *bs, ws.data_ptr(), nb, _stream(gt))
     check(rc, "pwc_sup_flow_loss_fwd")
     return out
@@ -1099,9 +903,8 @@ def sup_flow_loss_backward(pred: torch.Tensor, gt: torch.Tensor, mask: Optional[
     B, H, W, h, w = dims
     gp = torch.empty((B, 2, h, w), dtype=torch.float32, device=gt.device)
     with torch.cuda.device(gt.device):
-        nb = sup_flow_loss_workspace_bytes(*dims, backward=True)
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
-        rc = lib.pwc_sup_flow_loss_bwd(pred.data_ptr(), gt.data_ptr(), m.data_ptr() if m is not None else None, u8,
+        ws, nb = _scratch(sup_flow_loss_workspace_bytes(*dims, backward=True), gt.device)
+        rc = lib.pwc_sup_flow_loss_bwd(pred.data_ptr(), gt.data_ptr(), _ptr(m), u8,
                                        MASK_RULES[rule], fo.data_ptr(), g.data_ptr(), gp.data_ptr(), *dims, float(eps), *bs,
                                        ws.data_ptr(), nb, _stream(gt))
     check(rc, "pwc_sup_flow_loss_bwd")
@@ -1140,10 +943,8 @@ def _levels_host(preds, weights):
 def sup_multiscale_loss_workspace_bytes(B: int, H: int, W: int, sizes, with_images: bool) -> int:
     L = len(sizes)
     hw = (ctypes.c_int * (2 * L))(*[int(s) for hw_ in sizes for s in hw_])
-    n = _lib.load().pwc_sup_multiscale_loss_workspace_bytes(B, H, W, L, ctypes.cast(hw, ctypes.c_void_p), 1 if with_images else 0)
-    if n < 0:
-        raise ValueError("bad multiscale-loss geometry")
-    return int(n)
+    return _query_bytes(_lib.load().pwc_sup_multiscale_loss_workspace_bytes(B, H, W, L, ctypes.cast(hw, ctypes.c_void_p),
+                                                                          1 if with_images else 0), "multiscale-loss")
 
 
 def _ms_args(preds, gt, mask, images, weights, lambda_photo, lambda_smooth):
@@ -1156,9 +957,7 @@ def _ms_args(preds, gt, mask, images, weights, lambda_photo, lambda_smooth):
     if not 1 <= len(preds) <= SUP_MAX_LEVELS or len(weights) != len(preds):
         raise ValueError("1..%d flow levels with one weight each, got %d levels / %d weights" % (SUP_MAX_LEVELS, len(preds), len(weights)))
     preds = [_f32_dense(p, "flow level %d" % i, (B, 2) + tuple(p.shape[-2:]), gt.device)[0] for i, p in enumerate(preds)]
-    m, u8, bsm = _sup_mask(mask, B, H, W)
-    if m is not None and m.device != gt.device:
-        raise ValueError("masks must be on %s" % gt.device)
+    m, u8, bsm = _mask_arg(mask, B, H, W, gt.device, "raw", "masks")
     with_images = lambda_photo > 0.0 or lambda_smooth > 0.0
     img, bsi = None, 0
     if with_images:
@@ -1179,12 +978,10 @@ def sup_multiscale_loss(preds, gt: torch.Tensor, mask: Optional[torch.Tensor], i
     ptrs, bss, hw, wts = _levels_host(preds, weights)
     out = torch.empty(1 + 3 * L, dtype=torch.float32, device=gt.device)
     with torch.cuda.device(gt.device):
-        nb = sup_multiscale_loss_workspace_bytes(*dims, [p.shape[-2:] for p in preds], wi)
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
+        ws, nb = _scratch(sup_multiscale_loss_workspace_bytes(*dims, [p.shape[-2:] for p in preds], wi), gt.device)
         rc = lib.pwc_sup_multiscale_loss_fwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(bss, ctypes.c_void_p),
                                              ctypes.cast(hw, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p), L, gt.data_ptr(),
-                                             m.data_ptr() if m is not None else None, u8,
-                                             img.data_ptr() if img is not None else None, out.data_ptr(), *dims, float(eps),
+                                             _ptr(m), u8, _ptr(img), out.data_ptr(), *dims, float(eps),
                                              float(lambda_photo), float(lambda_smooth), *bs, ws.data_ptr(), nb, _stream(gt))
     check(rc, "pwc_sup_multiscale_loss_fwd")
     return out
@@ -1204,12 +1001,10 @@ def sup_multiscale_loss_backward(preds, gt: torch.Tensor, mask: Optional[torch.T
     grads = [torch.empty(tuple(p.shape), dtype=torch.float32, device=gt.device) for p in preds]
     gptrs = (ctypes.c_void_p * L)(*[t.data_ptr() for t in grads])
     with torch.cuda.device(gt.device):
-        nb = sup_multiscale_loss_workspace_bytes(*dims, [p.shape[-2:] for p in preds], wi)
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=gt.device)
+        ws, nb = _scratch(sup_multiscale_loss_workspace_bytes(*dims, [p.shape[-2:] for p in preds], wi), gt.device)
         rc = lib.pwc_sup_multiscale_loss_bwd(ctypes.cast(ptrs, ctypes.c_void_p), ctypes.cast(bss, ctypes.c_void_p),
                                              ctypes.cast(hw, ctypes.c_void_p), ctypes.cast(wts, ctypes.c_void_p), L, gt.data_ptr(),
-                                             m.data_ptr() if m is not None else None, u8,
-                                             img.data_ptr() if img is not None else None, fo.data_ptr(), g.data_ptr(),
+                                             _ptr(m), u8, _ptr(img), fo.data_ptr(), g.data_ptr(),
                                              ctypes.cast(gptrs, ctypes.c_void_p), *dims, float(eps), float(lambda_photo),
                                              float(lambda_smooth), *bs, ws.data_ptr(), nb, _stream(gt))
     check(rc, "pwc_sup_multiscale_loss_bwd")
@@ -1247,25 +1042,9 @@ ROBUST_CODES = {"huber": 0, "l1": 1}   # anything else: the plain mean (code 2),
 def _flow_arg(flow: torch.Tensor, name: str = "flow_full") -> Tuple[torch.Tensor, int]:
     if not isinstance(flow, torch.Tensor) or not flow.is_cuda:
         raise PwcHipError("%s must be a ROCm device tensor: the epipolar path has no CPU fallback" % name)
-    if flow.dim() != 4 or flow.shape[1] != 2 or flow.dtype != torch.float32:
+    if flow.dim() != 4:
         raise ValueError("%s must be float32 [B,2,H,W], got %s %s" % (name, flow.dtype, tuple(flow.shape)))
-    flow = densify(flow)
-    return flow, _plane_dense(flow, name)
-
-
-def _nonzero_mask_arg(mask: Optional[torch.Tensor], B: int, H: int, W: int, device) -> Tuple[Optional[torch.Tensor], int]:
-    """Image mask as pwc_epipolar_pairs reads it (value != 0, numpy's astype(bool)): bool / uint8 as bytes, float32 as is."""
-    if mask is None:
-        return None, 0
-    if mask.dim() == 4:
-        mask = mask[:, 0]
-    if tuple(mask.shape) != (B, H, W) or mask.device != device:
-        raise ValueError("img_mask_bhw must be [B,H,W] or [B,1,H,W] = %s on %s, got %s" % ((B, H, W), device, tuple(mask.shape)))
-    if mask.dtype in (torch.bool, torch.uint8):
-        return mask.contiguous().view(torch.uint8), 1
-    if mask.dtype == torch.float32:
-        return mask.contiguous(), 0
-    return (mask != 0).contiguous().view(torch.uint8), 1
+    return _f32_dense(flow, name, (flow.shape[0], 2) + tuple(flow.shape[2:]), flow.device)
 
 
 def epipolar_pairs(flow: torch.Tensor, stride: int = 4, mask: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
@@ -1277,12 +1056,12 @@ def epipolar_pairs(flow: torch.Tensor, stride: int = 4, mask: Optional[torch.Ten
     stride = int(stride)
     if stride < 1:
         raise ValueError("stride must be >= 1")
-    m, u8 = _nonzero_mask_arg(mask, B, H, W, flow.device)
+    m, u8, _ = _mask_arg(mask, B, H, W, flow.device, "nonzero", "img_mask_bhw")
     cap = -(-H // stride) * -(-W // stride)
     pts = torch.empty((B, cap, 4), dtype=torch.float64, device=flow.device)
     n = torch.empty(B, dtype=torch.int32, device=flow.device)
     with torch.cuda.device(flow.device):
-        rc = lib.pwc_epipolar_pairs(flow.data_ptr(), m.data_ptr() if m is not None else None, u8, pts.data_ptr(), n.data_ptr(),
+        rc = lib.pwc_epipolar_pairs(flow.data_ptr(), _ptr(m), u8, pts.data_ptr(), n.data_ptr(),
                                     B, H, W, stride, bsf, H * W, _stream(flow))
     check(rc, "pwc_epipolar_pairs")
     return pts, n
@@ -1310,10 +1089,7 @@ def epipolar_ransac(pts: torch.Tensor, n: torch.Tensor, idx: torch.Tensor, thres
     best = torch.empty(B, dtype=torch.int32, device=dev)
     counts = torch.empty((B, iters), dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        nb = lib.pwc_epipolar_ransac_workspace_bytes(B, iters)
-        if nb < 0:
-            raise ValueError("bad RANSAC geometry")
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+        ws, nb = _scratch(_query_bytes(lib.pwc_epipolar_ransac_workspace_bytes(B, iters), "RANSAC"), dev)
         rc = lib.pwc_epipolar_ransac(pts.data_ptr(), n.contiguous().data_ptr(), cap, idx.data_ptr(), ibs, B, iters, float(thresh),
                                      F.data_ptr(), ok.data_ptr(), best.data_ptr(), counts.data_ptr(), ws.data_ptr(), nb,
                                      torch.cuda.current_stream(dev).cuda_stream)
@@ -1366,12 +1142,9 @@ def epipolar_mask(flow: torch.Tensor, F: torch.Tensor, ok: torch.Tensor, tau: fl
     if dist_out is not None and (tuple(dist_out.shape) != (B, H, W) or dist_out.dtype != torch.float64 or not dist_out.is_contiguous()):
         raise ValueError("dist_out must be contiguous float64 %s" % ((B, H, W),))
     with torch.cuda.device(dev):
-        nb = lib.pwc_epipolar_mask_workspace_bytes(B, H, W)
-        if nb < 0:
-            raise ValueError("bad mask geometry")
-        ws = torch.empty((nb + 7) // 8, dtype=torch.int64, device=dev)
+        ws, nb = _scratch(_query_bytes(lib.pwc_epipolar_mask_workspace_bytes(B, H, W), "mask"), dev)
         rc = lib.pwc_epipolar_mask(flow.data_ptr(), F.data_ptr(), ok.data_ptr(), mask.data_ptr(), thr.data_ptr(),
-                                   dist_out.data_ptr() if dist_out is not None else None, B, H, W, float(tau), float(keep_ratio),
+                                   _ptr(dist_out), B, H, W, float(tau), float(keep_ratio),
                                    float(min_keep), bsf, ws.data_ptr(), nb, _stream(flow))
     check(rc, "pwc_epipolar_mask")
     return mask, thr
@@ -1387,17 +1160,12 @@ def _loss_args(flow, F, ok, valid_mask):
         if okt.numel() not in (1, B):
             raise ValueError("ok must hold 1 or B values")
         obs = 1 if okt.numel() == B and B > 1 else 0
-    m, u8, bsm = _mask_arg(valid_mask, B, H, W)
-    if m is not None and m.device != flow.device:
-        raise ValueError("valid_mask must be on %s" % flow.device)
+    m, u8, bsm = _mask_arg(valid_mask, B, H, W, flow.device, "threshold", "valid_mask")
     return flow, bsf, (B, H, W), Fd, fbs, okt, obs, m, u8, bsm
 
 
 def _loss_workspace(B, H, W, device):
-    nb = _lib.load().pwc_epipolar_loss_workspace_bytes(B, H, W)
-    if nb < 0:
-        raise ValueError("bad loss geometry")
-    return torch.empty((nb + 7) // 8, dtype=torch.int64, device=device), nb
+    return _scratch(_query_bytes(_lib.load().pwc_epipolar_loss_workspace_bytes(B, H, W), "loss"), device)
 
 
 def epipolar_loss(flow: torch.Tensor, F, ok=None, valid_mask: Optional[torch.Tensor] = None, robust: str = "huber",
@@ -1409,8 +1177,7 @@ def epipolar_loss(flow: torch.Tensor, F, ok=None, valid_mask: Optional[torch.Ten
     out = torch.empty(1, dtype=torch.float32, device=flow.device)
     with torch.cuda.device(flow.device):
         ws, nb = _loss_workspace(B, H, W, flow.device)
-        rc = lib.pwc_epipolar_loss_fwd(flow.data_ptr(), Fd.data_ptr(), fbs, okt.data_ptr() if okt is not None else None, obs,
-                                       m.data_ptr() if m is not None else None, u8, out.data_ptr(), B, H, W,
+        rc = lib.pwc_epipolar_loss_fwd(flow.data_ptr(), Fd.data_ptr(), fbs, _ptr(okt), obs, _ptr(m), u8, out.data_ptr(), B, H, W,
                                        ROBUST_CODES.get(robust, 2), float(delta), float(weight), bsf, bsm, ws.data_ptr(), nb,
                                        _stream(flow))
     check(rc, "pwc_epipolar_loss_fwd")
@@ -1426,9 +1193,8 @@ def epipolar_loss_backward(flow: torch.Tensor, F, ok, valid_mask: Optional[torch
     gf = torch.empty((B, 2, H, W), dtype=torch.float32, device=flow.device)
     with torch.cuda.device(flow.device):
         ws, nb = _loss_workspace(B, H, W, flow.device)
-        rc = lib.pwc_epipolar_loss_bwd(flow.data_ptr(), Fd.data_ptr(), fbs, okt.data_ptr() if okt is not None else None, obs,
-                                       m.data_ptr() if m is not None else None, u8, g.data_ptr(), gf.data_ptr(), B, H, W,
-                                       ROBUST_CODES.get(robust, 2), float(delta), float(weight), bsf, bsm, ws.data_ptr(), nb,
+        rc = lib.pwc_epipolar_loss_bwd(flow.data_ptr(), Fd.data_ptr(), fbs, _ptr(okt), obs, _ptr(m), u8, g.data_ptr(), gf.data_ptr(),
+                                       B, H, W, ROBUST_CODES.get(robust, 2), float(delta), float(weight), bsf, bsm, ws.data_ptr(), nb,
                                        _stream(flow))
     check(rc, "pwc_epipolar_loss_bwd")
     return gf

@@ -11,16 +11,8 @@ from typing import Optional
 import torch
 
 from . import _lib
-from ._lib import FLAG_ACT_LEAKY, PwcHipError, check
-
-
-def _stream(t: torch.Tensor) -> int:
-    return torch.cuda.current_stream(t.device).cuda_stream
-
-
-def _require_device(t: torch.Tensor, name: str) -> None:
-    if not t.is_cuda:
-        raise PwcHipError("%s is on %s: the HIP path needs device tensors and has no CPU fallback" % (name, t.device))
+from ._args import _bias_arg, _require_device, _stream
+from ._lib import FLAG_ACT_LEAKY, check
 
 
 def c8_shape(B: int, C: int, H: int, W: int):
@@ -125,8 +117,7 @@ def conv3x3_f16(x: torch.Tensor, wpacked: torch.Tensor, bias: torch.Tensor, cin:
     need = lib.pwc_conv3x3_f16_packed_bytes_split(cin, cout) if split_w else lib.pwc_conv3x3_f16_packed_bytes(cin, cout)
     if wpacked.dtype != torch.float16 or wpacked.numel() * 2 != need or wpacked.device != x.device:
         raise ValueError("packed filters do not match Cin=%d Cout=%d" % (cin, cout))
-    if bias.dtype != torch.float32 or bias.numel() != cout or bias.device != x.device or not bias.is_contiguous():
-        raise ValueError("bias must be float32[%d] on %s" % (cout, x.device))
+    _bias_arg(bias, cout, x.device)
     with torch.cuda.device(x.device):
         rc = lib.pwc_conv2d_f16_fwd(x.data_ptr(), wpacked.data_ptr(), bias.data_ptr(), out.data_ptr(), B, cin, H, W, cout,
                                     stride, dilation, (FLAG_ACT_LEAKY if leaky_slope is not None else 0) |
