@@ -32,14 +32,20 @@ def hartley(p):
     return (T @ p.T).T, T
 
 
-def eight_point(p1, p2):
-    """:210-225 -- the right singular vector of the min(n, 9)-th largest singular value (numpy's thin SVD; for n = 8 that is
-    NOT the null vector), rank 2, denormalise, scale by F[2,2] or the Frobenius norm."""
+def design_matrix(p1, p2):
+    """:211-216 -- the n x 9 system of the Hartley-normalised pairs and the two normalisations: (A, T1, T2)."""
     q1, T1 = hartley(p1)
     q2, T2 = hartley(p2)
     u, v, up, vp = q1[:, 0], q1[:, 1], q2[:, 0], q2[:, 1]
-    A = np.column_stack([u * up, v * up, up, vp * u, vp * v, vp, u, v, np.ones_like(u)])
-    vt = np.linalg.svd(A, full_matrices=False)[2]
+    return np.column_stack([u * up, v * up, up, vp * u, vp * v, vp, u, v, np.ones_like(u)]), T1, T2
+
+
+def eight_point(p1, p2, full_matrices=False):
+    """:210-225 -- the right singular vector of the min(n, 9)-th largest singular value (numpy's thin SVD; for n = 8 that is
+    NOT the null vector), rank 2, denormalise, scale by F[2,2] or the Frobenius norm.  full_matrices=True is NOT the reference:
+    it always takes the 9th vector, the mistake a test of the n = 8 refit has to be able to see."""
+    A, T1, T2 = design_matrix(p1, p2)
+    vt = np.linalg.svd(A, full_matrices=full_matrices)[2]
     Fn = vt[-1].reshape(3, 3)
     U, S, Vt = np.linalg.svd(Fn)
     Fn = U @ np.diag([S[0], S[1], 0.0]) @ Vt
@@ -66,23 +72,32 @@ def index_table(N, seed, iters):
     return np.stack([rng.choice(N, size=8, replace=False) for _ in range(iters)]).astype(np.int32)
 
 
-def ransac(p1, p2, max_iters=2000, thresh=0.5, seed=0):
-    """:236-258 -> dict(F, ok, best, counts).  Fails (ok False) when N < 8 or the best count < 8."""
+def ransac(p1, p2, max_iters=2000, thresh=0.5, seed=0, idx=None):
+    """:236-258 -> dict(F, ok, best, counts, hyps, idx).  Fails (ok False) when N < 8 or the best count < 8.
+    idx [iters,8] replaces the sampler's table (max_iters and seed are then unused).  A row of it that holds an index outside
+    [0, N) is the one input the reference cannot have: the product documents it as a NaN hypothesis with count 0, and so it is here."""
     N = p1.shape[0]
+    if idx is not None:
+        max_iters = len(idx)
     if N < 8:
         return dict(F=None, ok=False, best=-1, counts=np.zeros(max_iters, np.int64))
-    idx = index_table(N, seed, max_iters)
+    if idx is None:
+        idx = index_table(N, seed, max_iters)
     counts = np.empty(max_iters, np.int64)
     Fs = []
     for i in range(max_iters):
+        if idx[i].min() < 0 or idx[i].max() >= N:
+            Fs.append(np.full((3, 3), np.nan))
+            counts[i] = 0
+            continue
         Fc = eight_point(p1[idx[i]], p2[idx[i]])
         Fs.append(Fc)
         counts[i] = int((sampson(Fc, p1, p2) < thresh).sum())
     best = int(np.argmax(counts))            # first of the strictly largest
     if counts[best] < 8:
-        return dict(F=None, ok=False, best=best, counts=counts)
+        return dict(F=None, ok=False, best=best, counts=counts, hyps=np.stack(Fs), idx=idx)
     inl = sampson(Fs[best], p1, p2) < thresh
-    return dict(F=eight_point(p1[inl], p2[inl]), ok=True, best=best, counts=counts, hyps=np.stack(Fs))
+    return dict(F=eight_point(p1[inl], p2[inl]), ok=True, best=best, counts=counts, hyps=np.stack(Fs), idx=idx)
 
 
 def distance_map(flow_hw2, Fm):
