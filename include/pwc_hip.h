@@ -30,6 +30,10 @@
  *                       train_fundamental.py:169-382 (the hard epipolar mask and soft Sampson penalty, :459-483)
  *   pwc_fb_metrics      _forward_backward_consistency / _oob_ratio train_pseudo.py:178-236, forward_backward_cycle / oob_ratio
  *                       train_fundamental.py:397-428 (the no-ground-truth validation metrics, on two given flows)
+ *   pwc_flow_stats / pwc_flow_color   flow_to_color pwc_extract_flow.py:58-123 (the colour-wheel image save_outputs writes, :182-190)
+ *                       and calculate_dominant_direction topview.py:122-134
+ *   pwc_flow_quiver     the arrow grid of create_quiver_frame pwc_extract_flow_video.py:94-135 and draw_flow_arrows topview.py:137-178
+ *                       (vectors, tips and flags; drawing stays with the caller)
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -492,6 +496,56 @@ int pwc_kitti_score(const void *flow_q, int n, int Hq, int Wq, int crop_h, int c
                     const void *gt, int gt_kind, const void *valid,
                     void *flow_out /* may be NULL */, void *workspace, int64_t workspace_bytes,
                     void *out /* float [n][2] */, void *stream);
+
+/* Flow pictures on the device (additions within ABI v13, csrc/pwc_flowviz.hip).  All three read the top-left crop_h x crop_w of
+ * flow [n][2][Hq][Wq] f32 (dense planes, batch stride in elements): the reference colours and draws the cropped quarter-resolution
+ * flow.  fp32 with no fused multiply-add, divisions and square roots correctly rounded; no atomics, so every output is
+ * bit-reproducible; nothing allocates or synchronises.  Behaviour on NaN / infinite flow is undefined, as in the reference.
+ *
+ * pwc_flow_stats: per sample the 16-byte record rec[b] = {float max radius, int32 count, float mean u, float mean v}:
+ *   max radius = max over the crop of sqrtf(u*u + v*v) of (u, v) AFTER the optional clip (use_clip != 0, flow_to_color lines 65-69):
+ *        rad = sqrtf(u*u + v*v);  k = clip_flow / fmaxf(fmaxf(rad, 1e-5f), clip_flow);  u = u * k;  v = v * k;
+ *   count / means over the pixels whose UNCLIPPED sqrtf(u*u + v*v) > threshold (calculate_dominant_direction): each fp32 u and v is
+ *        added in fp64, mean = (float)(sum / count); both means are 0 when count == 0 (the reference returns [0, 0]).
+ *   Each 16 x 64 tile leaves {fp64 sum u, fp64 sum v, int64 count, fp32 max} in the workspace, summed in a fixed tree order, and one
+ *   final workgroup per sample adds that sample's tiles in tile order.  workspace: device, 8-byte aligned,
+ *   pwc_flow_stats_workspace_bytes(n, crop_h, crop_w) = 32 * n * tiles per sample bytes (-1 for a non-positive size).
+ * pwc_flow_color: out uint8 [n][crop_h][crop_w][3], R G B, contiguous, at ANY byte address (3 bytes per pixel: a sample starts
+ *   unaligned in general); only those n*crop_h*crop_w*3 bytes are written.  rec is the record of pwc_flow_stats for the same flow, crop
+ *   and clip (read on the device).  Per pixel, flow_to_color operation for operation, with (u, v) after the same optional clip:
+ *        rad = sqrtf(u*u + v*v);  ang = atan2f(-v, -u) / (float)pi;  fk = (ang + 1.f) / 2.f * 54.f + 1.f;
+ *        k0 = ((int)floorf(fk) - 1) % 55;  k1 = (k0 + 1) % 55;  f = fk - floorf(fk);
+ *        col = (1.f - f) * wheel[k0][c] + f * wheel[k1][c]      wheel = the 55-entry make_colorwheel (RY 15, YG 6, GC 4, CB 11, BM 13,
+ *                                                               MR 6) as (float)entry / 255.f
+ *        rn = clip(rad / (rec[b].max + 1e-5f), 0, 1);  col = 1.f - rn * (1.f - col);  out = (uint8)(clip(col, 0, 1) * 255.f)  (truncation)
+ *   The wheel is NOT continuous where the angle wraps (54 intervals over 55 entries): (u > 0, v = +0.0) gives (255, 0, 0), (u > 0,
+ *   v = -0.0) gives (255, 0, 43); the sign of a zero reaches atan2f unchanged.  1 - f is exact (f is the fraction of an fp32 fk >= 1), so
+ *   a channel whose two wheel entries are 255 is exactly 255 before the attenuation.
+ * pwc_flow_quiver: the arrow grid at y = 0, step, ... < frame_h and x = 0, step, ... < frame_w (Gy = ceil(frame_h / step), Gx alike):
+ *        (dx, dy) = value of cv2.resize(plane, (frame_w, frame_h)) (INTER_LINEAR, float path: geometry in double then float,
+ *                   horizontal pass, then vertical pass) at (y, x), times (vec_sx, vec_sy); when (crop_h, crop_w) == (frame_h,
+ *                   frame_w) the flow's own value (cv::resize copies);
+ *        keep  = !(sqrtf(dx*dx + dy*dy) < min_mag);
+ *        tip   = ((float)x + dx * gain, (float)y + dy * gain) to int: tip_rule 0 = round half to even (int(round(.)) of
+ *                create_quiver_frame, gain = 1 / max(scale, 1e-6)), tip_rule 1 = toward zero (int(.) of draw_flow_arrows, gain = scale);
+ *        aligned = 1 when dominant is NULL or the zero vector, else acosf(clip(dot(unit(dx, dy), unit(dominant)), -1, 1)) * 180.f /
+ *                (float)pi < angle_threshold (draw_flow_arrows lines 157-171; 0 for a zero (dx, dy)).
+ *   dominant: NULL, or device floats, sample b's (u, v) at dominant[b * dom_stride] and the next float (dom_stride 4 and rec + 2 reads
+ *   the means of pwc_flow_stats).  vec float [n][Gy][Gx][2], tip int32 [n][Gy][Gx][2] (x, y), flags uint8 [n][Gy][Gx] (bit 0 keep,
+ *   bit 1 aligned).
+ * PWC_EINVAL, nothing launched: a null pointer, non-positive sizes, crop_h > Hq or crop_w > Wq, bstride < 2*Hq*Wq, n*crop_h*crop_w*3
+ * >= 2^31, 2*Hq*Wq >= 2^31, n > 65535, use_clip with clip_flow <= 0, step < 1, tip_rule not 0 or 1, dom_stride < 2, more than 65535
+ * tile or grid rows, a workspace that is too small.  PWC_EALIGN, nothing launched: flow / rec / dominant not 4-byte aligned, workspace /
+ * vec / tip not 8-byte aligned. */
+int64_t pwc_flow_stats_workspace_bytes(int n, int crop_h, int crop_w);
+int pwc_flow_stats(const void *flow, int n, int Hq, int Wq, int crop_h, int crop_w, int64_t bstride, int use_clip, float clip_flow,
+                   float threshold, void *workspace, int64_t workspace_bytes, void *rec /* [n][4] 4-byte words */, void *stream);
+int pwc_flow_color(const void *flow, int n, int Hq, int Wq, int crop_h, int crop_w, int64_t bstride, int use_clip, float clip_flow,
+                   const void *rec, void *out /* uint8 [n][crop_h][crop_w][3] */, void *stream);
+int pwc_flow_quiver(const void *flow, int n, int Hq, int Wq, int crop_h, int crop_w, int64_t bstride, int frame_h, int frame_w,
+                    int step, float vec_sx, float vec_sy, float gain, int tip_rule, float min_mag,
+                    const void *dominant /* may be NULL */, int64_t dom_stride, float angle_threshold,
+                    void *vec, void *tip, void *flags, void *stream);
 
 /* ---- fp16 convolution (first piece of the half-precision path, BASELINE configs 3-4) --------------------------
  * Activations are channel-blocked "c8": [B][ceil(C/8)][H][W][8] halves, channels past C zero; only the batch

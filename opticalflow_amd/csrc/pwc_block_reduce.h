@@ -4,6 +4,7 @@
 //                  KITTI score)
 //   wave_block_sum xor tree inside each wave, then the waves in ascending order (epipolar refit, threshold and loss)
 // Integer sums are order-free; they ride along in whichever form the kernel uses.
+// wave_block_max is the maximum of one float per lane (flow statistics); a maximum has no order to keep.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
@@ -87,6 +88,26 @@ __device__ __forceinline__ void wave_block_sum(WaveLds<T, NT, KMAX> &lds, T (&v)
         for (int o = 1; o < NT / 64; ++o) s += lds.v[o * K + k];
         v[k] = s;
     }
+}
+
+// workgroup maximum of one float per lane (flow statistics): xor tree inside each wave, then the waves through lds.  A maximum of
+// ordinary numbers does not depend on the order, so no order is promised; the result is in every lane.  Barriers as wave_block_sum.
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    return v;
+}
+
+template <int NT>
+__device__ __forceinline__ float wave_block_max(WaveLds<float, NT, 1> &lds, float v) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    v = wave_max(v);
+    __syncthreads();
+    if (lane == 0) lds.v[wv] = v;
+    __syncthreads();
+    float m = lds.v[0];
+    for (int o = 1; o < NT / 64; ++o) m = fmaxf(m, lds.v[o]);
+    return m;
 }
 
 // what a tile workgroup leaves in the workspace, and what the finish kernel puts in the workspace head

@@ -20,7 +20,7 @@ restatement is pinned by hand-computed known-answer vectors and an independent s
 (tests/test_harness.py), not against cv2: "parity unpinned" w.r.t. an actual cv2 build (whose SIMD / IPP variants
 are documented to match the scalar code above).
 
-CLI:  python -m opticalflow_amd.harness im1.png im2.png out.flo [--weights pwc_net.pth.tar]
+CLI:  python -m opticalflow_amd.harness im1.png im2.png out.flo [--weights pwc_net.pth.tar] [--png out.png]
 """
 from __future__ import annotations
 
@@ -145,12 +145,18 @@ def main(argv=None) -> int:
                          "mode) instead of the native /C correlation that checkpoints are trained with")
     ap.add_argument("--align-corners", action="store_true",
                     help="warp with grid_sample(align_corners=True) (torch < 1.3 behaviour, what the published weights saw)")
+    ap.add_argument("--png", default=None, metavar="PATH",
+                    help="also write the colour-wheel image of the flow (pwc_extract_flow.py's flow_to_color), made on the device")
     args = ap.parse_args(argv)
     from .pwcnet import pwc_dc_net
     net = pwc_dc_net(args.weights, normalize_corr=not args.cpu_fallback_semantics, align_corners=args.align_corners)
     net = net.cuda().eval()
     flo = estimate_flow(net, read_image(args.im1), read_image(args.im2))
     write_flo(args.out, flo.cpu())
+    if args.png:
+        from .flowio import write_png8_rgb
+        from .flowviz import flow_to_color
+        write_png8_rgb(args.png, flow_to_color(flo.permute(2, 0, 1).unsqueeze(0).contiguous())[0])
     return 0
 
 

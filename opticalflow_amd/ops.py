@@ -555,6 +555,108 @@ def kitti_score(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, out_
     return out
 
 
+def _flow_crop_arg(flow: torch.Tensor, crop) -> Tuple[int, int, int, int, int, int]:
+    """The [n,2,Hq,Wq] float32 device flow of the picture operators and its top-left crop -> (n, Hq, Wq, crop_h, crop_w, batch stride)."""
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError("flow must be [n,2,Hq,Wq], got %s" % (tuple(flow.shape),))
+    if flow.dtype != torch.float32:
+        raise TypeError("flow must be float32, got %s" % flow.dtype)
+    n, _, Hq, Wq = flow.shape
+    ch, cw = (Hq, Wq) if crop is None else (int(crop[0]), int(crop[1]))
+    if n < 1 or not (1 <= ch <= Hq and 1 <= cw <= Wq):
+        raise ValueError("crop %dx%d does not fit the %dx%d map (or the batch is empty)" % (ch, cw, Hq, Wq))
+    return n, Hq, Wq, ch, cw, _plane_dense(flow, "flow")
+
+
+def _clip_arg(clip_flow: Optional[float]) -> Tuple[int, float]:
+    if clip_flow is None:
+        return 0, 0.0
+    if not float(clip_flow) > 0.0:
+        raise ValueError("clip_flow must be positive, got %r" % (clip_flow,))
+    return 1, float(clip_flow)
+
+
+def flow_stats_workspace_bytes(n: int, crop_h: int, crop_w: int) -> int:
+    return _query_bytes(_lib.load().pwc_flow_stats_workspace_bytes(n, crop_h, crop_w), "flow-stats")
+
+
+def flow_stats(flow: torch.Tensor, crop: Optional[Tuple[int, int]] = None, clip_flow: Optional[float] = None, threshold: float = 1.0,
+               out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 [n,4] records of pwc_flow_stats over the top-left `crop` of flow [n,2,Hq,Wq]: column 0 the maximum radius after the
+    optional clip_flow rescale (what flow_to_color normalises by), column 1 the int32 bits of the number of pixels whose magnitude is >
+    threshold (`.view(torch.int32)`), columns 2-3 their mean (u, v), zero when there are none (calculate_dominant_direction).
+    workspace: optional device tensor of flow_stats_workspace_bytes(n, crop_h, crop_w) bytes, 8-byte aligned (allocated when absent).
+    Device tensors only, no host synchronisation, bit-reproducible."""
+    n, Hq, Wq, ch, cw, bs = _flow_crop_arg(flow, crop)
+    use_clip, clip = _clip_arg(clip_flow)
+    dev = flow.device
+    out = _out_arg(out, (n, 4), torch.float32, dev, contiguous=True)
+    need = flow_stats_workspace_bytes(n, ch, cw)
+    if workspace is None:
+        workspace, _ = _scratch(need, dev)
+    wp, wb = _workspace_args(workspace, flow)
+    if wb < need:
+        raise ValueError("workspace has %d bytes, flow_stats needs %d" % (wb, need))
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_flow_stats(flow.data_ptr(), n, Hq, Wq, ch, cw, bs, use_clip, clip, float(threshold), wp, wb, out.data_ptr(),
+                                        _stream(flow))
+    check(rc, "pwc_flow_stats")
+    return out
+
+
+def flow_color(flow: torch.Tensor, stats: torch.Tensor, crop: Optional[Tuple[int, int]] = None, clip_flow: Optional[float] = None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """uint8 [n,crop_h,crop_w,3] RGB colour-wheel image of pwc_flow_color (flow_to_color, pwc_extract_flow.py:58-123); `stats` is
+    flow_stats' record of the same flow, crop and clip_flow, read on the device.  `out` may start at any byte address."""
+    n, Hq, Wq, ch, cw, bs = _flow_crop_arg(flow, crop)
+    use_clip, clip = _clip_arg(clip_flow)
+    dev = flow.device
+    if tuple(stats.shape) != (n, 4) or stats.dtype != torch.float32 or stats.device != dev or not stats.is_contiguous():
+        raise ValueError("stats must be the contiguous float32 [%d,4] record of flow_stats on %s" % (n, dev))
+    out = _out_arg(out, (n, ch, cw, 3), torch.uint8, dev, contiguous=True)
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_flow_color(flow.data_ptr(), n, Hq, Wq, ch, cw, bs, use_clip, clip, stats.data_ptr(), out.data_ptr(), _stream(flow))
+    check(rc, "pwc_flow_color")
+    return out
+
+
+def flow_quiver(flow: torch.Tensor, frame_h: int, frame_w: int, step: int, vec_scale: Tuple[float, float], gain: float, tip_rule: int,
+                min_mag: float, crop: Optional[Tuple[int, int]] = None, dominant: Optional[torch.Tensor] = None,
+                angle_threshold: float = 30.0, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None):
+    """(vec float32 [n,Gy,Gx,2], tip int32 [n,Gy,Gx,2], flags uint8 [n,Gy,Gx]) of pwc_flow_quiver: the arrow grid every `step` pixels
+    of a frame_h x frame_w frame, from the top-left `crop` of flow [n,2,Hq,Wq] resized like cv2.resize at the grid points only.
+    tip_rule 0 rounds half to even, 1 truncates; flags bit 0 = keep (magnitude not below min_mag), bit 1 = aligned with `dominant`
+    (float32 [n,2] on the device, rows may be strided, e.g. flow_stats(...)[:, 2:4]; None = every arrow aligned)."""
+    frame_h, frame_w, step, tip_rule = int(frame_h), int(frame_w), int(step), int(tip_rule)
+    if frame_h < 1 or frame_w < 1:
+        raise ValueError("frame size must be positive, got %dx%d" % (frame_h, frame_w))
+    if step < 1:
+        raise ValueError("step must be >= 1, got %d" % step)
+    if tip_rule not in (0, 1):
+        raise ValueError("tip_rule must be 0 (round half to even) or 1 (truncate), got %d" % tip_rule)
+    n, Hq, Wq, ch, cw, bs = _flow_crop_arg(flow, crop)
+    dev = flow.device
+    dom_stride = 0
+    if dominant is not None:
+        if tuple(dominant.shape) != (n, 2) or dominant.dtype != torch.float32 or dominant.device != dev or dominant.stride(1) != 1 \
+                or (n > 1 and dominant.stride(0) < 2):
+            raise ValueError("dominant must be float32 [%d,2] on %s with unit inner stride" % (n, dev))
+        dom_stride = max(int(dominant.stride(0)), 2)
+    gy, gx = (frame_h + step - 1) // step, (frame_w + step - 1) // step
+    o = out if out is not None else (None, None, None)
+    if len(o) != 3:
+        raise ValueError("out must be (vec, tip, flags)")
+    vec = _out_arg(o[0], (n, gy, gx, 2), torch.float32, dev, contiguous=True)
+    tip = _out_arg(o[1], (n, gy, gx, 2), torch.int32, dev, contiguous=True)
+    flags = _out_arg(o[2], (n, gy, gx), torch.uint8, dev, contiguous=True)
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_flow_quiver(flow.data_ptr(), n, Hq, Wq, ch, cw, bs, frame_h, frame_w, step, float(vec_scale[0]),
+                                         float(vec_scale[1]), float(gain), tip_rule, float(min_mag), _ptr(dominant), dom_stride,
+                                         float(angle_threshold), vec.data_ptr(), tip.data_ptr(), flags.data_ptr(), _stream(flow))
+    check(rc, "pwc_flow_quiver")
+    return vec, tip, flags
+
+
 def lattice_unsplit(x: torch.Tensor, batch: int, levels: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Inverse of `levels` nested split2 stores: [batch * 4**levels, C, h, w] (contiguous) -> [batch, C, h << levels, w << levels]."""
     if not x.is_cuda or x.dtype != torch.float32 or not x.is_contiguous() or x.dim() != 4 or x.shape[0] != batch * 4 ** levels:

@@ -19,9 +19,10 @@ import numpy as np
 import torch
 
 from .engine import PwcVideoPlan
+from .flowviz import Renderer, RenderSpec
 from .kitti import pad_to_64, unpad as _unpad
 
-__all__ = ["FlowStream", "frame_to_tensor", "flow_video"]
+__all__ = ["FlowStream", "RenderSpec", "frame_to_tensor", "flow_video", "flow_video_rendered"]
 
 
 def frame_to_tensor(frame: np.ndarray) -> torch.Tensor:
@@ -37,9 +38,13 @@ class FlowStream:
 
     ``net`` is an ``opticalflow_amd.PWCDCNet`` on the ROCm device.  ``batch`` frames are consumed per
     ``push``; ``batch=1`` is the reference's loop.  With ``use_graph`` each push is one HIP-graph replay.
+
+    ``render`` (a ``flowviz.RenderSpec``): every push also makes the colour image and / or the arrow grid of its flows, on the device
+    and, with ``use_graph``, inside the same replay; ``rendered`` then holds them (static buffers, like the flow: consume or clone
+    them before the next push).  Without ``render`` nothing changes.
     """
 
-    def __init__(self, net, batch: int, height: int, width: int, use_graph: bool = True):
+    def __init__(self, net, batch: int, height: int, width: int, use_graph: bool = True, render: Optional[RenderSpec] = None):
         params = {k: v.detach() for k, v in net.state_dict(keep_vars=True).items()}
         p0 = next(iter(params.values()))
         if not p0.is_cuda:
@@ -61,6 +66,14 @@ class FlowStream:
         self.use_graph = use_graph
         self._graph = None
         self._static = torch.empty((batch, 3, height, width), device=self.device, dtype=torch.float32)
+        self.renderer = Renderer(render, tuple(self.plan.flow_out.shape), self.device) if render is not None else None
+        self.rendered = None
+
+    def _push(self, frames: torch.Tensor) -> torch.Tensor:
+        flow = self.plan.push(frames)
+        if self.renderer is not None:
+            self.rendered = self.renderer.run(flow)
+        return flow
 
     def prime(self, frame: torch.Tensor) -> None:
         """First frame of the sequence, [1,3,H,W] or [3,H,W]."""
@@ -76,7 +89,7 @@ class FlowStream:
             frames = frames.unsqueeze(0)
         with torch.no_grad():
             if not self.use_graph:
-                return self.plan.push(frames.to(self.device, torch.float32))
+                return self._push(frames.to(self.device, torch.float32))
             if not self.plan.primed:
                 raise RuntimeError("FlowStream.push before prime(first_frame)")
             if tuple(frames.shape) != tuple(self._static.shape):
@@ -88,13 +101,13 @@ class FlowStream:
                 side = torch.cuda.Stream(device=self.device)
                 side.wait_stream(torch.cuda.current_stream(self.device))
                 with torch.cuda.stream(side):
-                    self.plan.push(self._static)
+                    self._push(self._static)
                 torch.cuda.current_stream(self.device).wait_stream(side)
                 for l, t in keep.items():
                     self.plan.pyr_a[l][0].copy_(t)
                 graph = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(graph):
-                    self.plan.push(self._static)
+                    self._push(self._static)
                 for l, t in keep.items():
                     self.plan.pyr_a[l][0].copy_(t)
                 self._graph = graph
@@ -121,3 +134,40 @@ def flow_video(net, frames: Iterable[np.ndarray], use_graph: bool = True) -> Ite
         flow = stream.push(tp.to(stream.device))
         flow = _unpad(flow, pads[0], pads[1])     # full-resolution pad, like the reference
         yield flow.squeeze(0).permute(1, 2, 0).contiguous().cpu().numpy()
+
+
+def flow_video_rendered(net, frames: Iterable[np.ndarray], color: bool = True, quiver: Optional[dict] = None, use_graph: bool = True,
+                        clip_flow: Optional[float] = None, dominant: bool = False, with_flow: bool = False) -> Iterator[dict]:
+    """flow_video that hands back pictures instead of the float flow: per consecutive pair a dict with "color" (h,w,3) uint8 RGB (the
+    colour wheel of pwc_extract_flow.py's flow_to_color) when `color`, and "vec" (Gy,Gx,2) float32, "tip" (Gy,Gx,2) int32, "flags"
+    (Gy,Gx) uint8 when `quiver` is given: the keyword arguments of flowviz.quiver_arrows (step, scale, min_mag, style, ...;
+    frame_hw defaults to the frame's size).  Both are made on the device from the same cropped quarter-resolution flow flow_video
+    yields, and only they are downloaded; with_flow=True adds "flow", exactly flow_video's array."""
+    stream: Optional[FlowStream] = None
+    for frame in frames:
+        t = frame_to_tensor(frame).unsqueeze(0)
+        tp, pad_h, pad_w = pad_to_64(t)
+        if stream is None:
+            dev = next(net.parameters()).device
+            hq, wq = tp.shape[2] // 4, tp.shape[3] // 4
+            crop = (hq - pad_h, wq - pad_w)           # the reference's unpad: the full-resolution pad off the quarter-resolution map
+            qkw = None
+            if quiver is not None:
+                qkw = dict(quiver)
+                qkw.setdefault("frame_hw", tuple(frame.shape[:2]))
+            spec = RenderSpec(color=color, clip_flow=clip_flow, quiver=qkw, dominant=dominant, crop=crop)
+            stream = FlowStream(net, 1, tp.shape[2], tp.shape[3], use_graph=use_graph, render=spec)
+            stream.prime(tp.to(dev))
+            continue
+        if tuple(tp.shape[2:]) != (stream.height, stream.width):
+            raise ValueError("frame size changed mid-stream")
+        flow = stream.push(tp.to(stream.device))
+        r, out = stream.rendered, {}
+        if r.color is not None:
+            out["color"] = r.color[0].cpu().numpy()
+        if r.arrows is not None:
+            out["vec"], out["tip"], out["flags"] = (a[0].cpu().numpy() for a in r.arrows)
+        if with_flow:
+            ch, cw = stream.renderer.crop
+            out["flow"] = flow[0, :, :ch, :cw].permute(1, 2, 0).contiguous().cpu().numpy()
+        yield out
