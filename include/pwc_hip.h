@@ -34,6 +34,8 @@
  *                       and calculate_dominant_direction topview.py:122-134
  *   pwc_flow_quiver     the arrow grid of create_quiver_frame pwc_extract_flow_video.py:94-135 and draw_flow_arrows topview.py:137-178
  *                       (vectors, tips and flags; drawing stays with the caller)
+ *   pwc_kitti_augment   KittiFlowDataset.__getitem__ data_processing_or.py:228-294 (reduced augmentation with cv2.warpAffine, random
+ *                       crop, horizontal flip) from the raw uint8 frames and the ground truth, only the cropped window computed
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -546,6 +548,58 @@ int pwc_flow_quiver(const void *flow, int n, int Hq, int Wq, int crop_h, int cro
                     int step, float vec_sx, float vec_sy, float gain, int tip_rule, float min_mag,
                     const void *dominant /* may be NULL */, int64_t dom_stride, float angle_threshold,
                     void *vec, void *tip, void *flags, void *stream);
+
+/* Training batches of KITTI on the device (addition within ABI v13, csrc/pwc_augment.hip): the "reduced augmentation" (small rotation /
+ * zoom / squeeze affine), the random crop and the horizontal flip of KittiFlowDataset (data_processing_or.py:228-294) in one launch,
+ * from the raw uint8 frames and the ground truth to the (x, flow, valid) train_one_epoch consumes.  Only the crop_h x crop_w window is
+ * computed.  cv2.warpAffine (INTER_LINEAR, BORDER_REFLECT_101) is DEFINED here by a restatement of OpenCV's classic fixed-point path
+ * (the one OpenCV used through 4.10); parity against an actual cv2 build is UNPINNED (cv2 is not available where this was written).
+ * Everything is integer arithmetic, or fp32 / fp64 with the expression order below and no fused multiply-add, so the result is
+ * bit-reproducible and bit-identical to tests/augment_oracle.py.
+ *
+ * Sources sit in fixed slots of Hs x Ws (the batch's largest size); sample b is stored densely in the top of its slot with ITS OWN ROW
+ * STRIDE W_b (KITTI frames are 370-376 x 1224-1242):
+ *   frames  uint8 [n][2][Hs*Ws*3], pixel (y, x) channel c of frame f of sample b at ((b*2 + f)*Hs*Ws + y*W_b + x)*3 + c, R G B
+ *   gt      gt_kind 0: float [n][2][Hs*Ws] (u plane, v plane), element y*W_b + x; valid = uint8 [n][Hs*Ws] (non-zero = valid) or NULL
+ *           (every pixel valid);  gt_kind 1: the KITTI PNG samples uint16 [n][Hs*Ws][3] in R, G, B order, decoded per tap as
+ *           u = ((float)R - 32768.f) / 64.f, v likewise from G, valid = (B != 0); valid must be NULL
+ *   params  DEVICE buffer, 8-byte aligned, one pwc_augment_params record (88 bytes) per sample:
+ *           m[6]  the INVERTED 2x3 matrix in fp64, as cv::warpAffine inverts the float32 M = [A | t] after converting it to double:
+ *                 D = M0*M4 - M1*M3; D = D ? 1/D : 0; A11 = M4*D; A22 = M0*D; M0 = A11; M1 *= -D; M3 *= -D; M4 = A22;
+ *                 b1 = -M0*M2 - M1*M5; b2 = -M3*M2 - M4*M5; M2 = b1; M5 = b2
+ *           a[4]  the float32 linear part A = {A00, A01, A10, A11} of the forward matrix (applied to the flow vectors)
+ *           y0, x0  crop origin in the (warped) frame;  h, w = H_b, W_b the sample's own size;  warp, flip  flags (non-zero = on)
+ *   x float [n][6][crop_h][crop_w] (channels 0-2 frame 1, 3-5 frame 2, in [0, 1]), flow float [n][2][crop_h][crop_w],
+ *   valid_out float [n][1][crop_h][crop_w] (0 / 1), status int32 [n]; all dense.
+ * Per output pixel (y', x') of sample b:
+ *   xs = flip ? crop_w - 1 - x' : x';  (Y, X) = (y0 + y', x0 + xs)      the reference crops after warping and flips after cropping
+ *   warp == 0: the sources are read at (Y, X):  x = (float)byte / 255.f, flow = the (decoded) ground truth, valid = (source != 0)
+ *   warp != 0: fp64 and int32, rint = round half to even (OpenCV's saturate_cast<int>(double)):
+ *        ad = rint(M0 * X * 1024);  bd = rint(M3 * X * 1024);  X0 = rint((M1 * Y + M2) * 1024) + 16;  Y0 = rint((M4 * Y + M5) * 1024) + 16
+ *        Xq = (X0 + ad) >> 5;  Yq = (Y0 + bd) >> 5  (arithmetic);  sx = Xq >> 5;  sy = Yq >> 5;  fx = Xq & 31;  fy = Yq & 31
+ *        taps p00 (sy, sx), p01 (sy, sx+1), p10 (sy+1, sx), p11 (sy+1, sx+1), every index mapped by BORDER_REFLECT_101 over the
+ *        sample's own W_b / H_b (period 2(len-1), any number of reflections, len == 1 -> 0)
+ *        images  v = (p00*(32-fy)*(32-fx) + p01*(32-fy)*fx + p10*fy*(32-fx) + p11*fy*fx + 512) >> 10;  x = (float)v / 255.f
+ *        flow    gx = (float)fx / 32.f, gy alike;  w00 = (1-gy)*(1-gx), w01 = (1-gy)*gx, w10 = gy*(1-gx), w11 = gy*gx;
+ *                f = ((p00*w00 + p01*w01) + p10*w10) + p11*w11 per plane;  u' = A00*fu + A01*fv;  v' = A10*fu + A11*fv
+ *        valid   the 0/1 taps with the same weights and order (exact), valid = (sum > 0.5f) ? 1 : 0 (exactly 0.5 is NOT valid)
+ *   flip: u' = u' * -1.0f last.
+ * A record the kernel cannot honour -- h not in [1, Hs], w not in [1, Ws], crop_h > h, crop_w > w, or a crop origin outside
+ * [0, h-crop_h] x [0, w-crop_w] -- never becomes a gather: that sample's outputs are zeros and status[b] = 1 (0 otherwise).  A matrix
+ * with non-finite or huge entries is harmless: conversions saturate, sums wrap, and every tap index is reflected into the sample.
+ * The reference's "upsize first when the frame is smaller than the crop" branch (:259-268) is not provided.
+ * PWC_EINVAL, nothing launched: a null pointer (valid may be NULL), non-positive sizes, n > 65535, Hs or Ws > 32767 (OpenCV's short
+ * coordinate saturation is not restated), crop_h > Hs or crop_w > Ws, gt_kind not 0 or 1, valid != NULL with gt_kind 1.
+ * PWC_EALIGN, nothing launched: x / flow / valid_out / status / a float gt not 4-byte aligned, a uint16 gt not 2-byte aligned, params not
+ * 8-byte aligned. */
+typedef struct pwc_augment_params {
+    double m[6];
+    float a[4];
+    int32_t y0, x0, h, w, warp, flip;
+} pwc_augment_params;
+int pwc_kitti_augment(const void *frames, const void *gt, int gt_kind, const void *valid /* may be NULL */, int n, int Hs, int Ws,
+                      int crop_h, int crop_w, const void *params /* device pwc_augment_params [n] */, void *x, void *flow,
+                      void *valid_out, void *status /* int32 [n] */, void *stream);
 
 /* ---- fp16 convolution (first piece of the half-precision path, BASELINE configs 3-4) --------------------------
  * Activations are channel-blocked "c8": [B][ceil(C/8)][H][W][8] halves, channels past C zero; only the batch

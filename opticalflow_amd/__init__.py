@@ -7,5 +7,7 @@ from .flowio import read_flo, save_outputs, write_flo, write_png8_rgb  # noqa: F
 from . import validation  # noqa: F401
 from . import flowviz  # noqa: F401
 from .flowviz import dominant_direction, flow_to_color, quiver_arrows  # noqa: F401
+from . import augment  # noqa: F401
+from .augment import DeviceAugmenter, augment_batch  # noqa: F401
 
 __version__ = "0.1.0"

@@ -16,8 +16,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._args import (_bias_arg, _dtype_code, _f32_dense, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr, _query_bytes, _scratch,
-                    _stream, _workspace_args, densify)
+from ._args import (_bias_arg, _dtype_code, _f32_dense, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr, _query_bytes,
+                    _require_device, _scratch, _stream, _workspace_args, densify)
 from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F32, PwcHipError, check)
 
 def corr_output_shape(C: int, H: int, W: int, pad_size: int, kernel_size: int, max_displacement: int,
@@ -655,6 +655,57 @@ def flow_quiver(flow: torch.Tensor, frame_h: int, frame_w: int, step: int, vec_s
                                          float(angle_threshold), vec.data_ptr(), tip.data_ptr(), flags.data_ptr(), _stream(flow))
     check(rc, "pwc_flow_quiver")
     return vec, tip, flags
+
+
+AUGMENT_RECORD_BYTES = 88      # sizeof(pwc_augment_params): six fp64, four fp32, six int32
+
+
+def kitti_augment(frames: torch.Tensor, gt: torch.Tensor, params: torch.Tensor, crop_hw: Tuple[int, int],
+                  valid: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                  status: Optional[torch.Tensor] = None):
+    """(x float32 [n,6,ch,cw], flow float32 [n,2,ch,cw], valid float32 [n,1,ch,cw], status int32 [n]) of pwc_kitti_augment: the reduced
+    augmentation, crop and flip of KittiFlowDataset in one launch.  frames: uint8 [n,2,Hs,Ws,3] slots; gt: torch.uint16 [n,Hs,Ws,3]
+    (the KITTI PNG samples, `valid` must be None) or float32 [n,2,Hs,Ws] with `valid` None / bool or uint8 [n,Hs,Ws]; sample b lies
+    densely at the start of each of its slots with its own row stride W_b.  params: uint8 [n,88] device records (pwc_augment_params;
+    opticalflow_amd.augment builds and validates them).  status[b] != 0 marks a record the kernel refused (that sample's outputs are
+    zeros).  Device tensors only, no host synchronisation, bit-reproducible."""
+    if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3 or frames.dtype != torch.uint8 or not frames.is_contiguous():
+        raise ValueError("frames must be contiguous uint8 [n,2,Hs,Ws,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+    _require_device(frames, "frames")
+    n, _, Hs, Ws, _ = frames.shape
+    dev = frames.device
+    ch, cw = int(crop_hw[0]), int(crop_hw[1])
+    if n < 1 or not (1 <= ch <= Hs and 1 <= cw <= Ws):
+        raise ValueError("crop %dx%d does not fit the %dx%d slot (or the batch is empty)" % (ch, cw, Hs, Ws))
+    if gt.dtype == torch.uint16:
+        kind, want = 1, (n, Hs, Ws, 3)
+        if valid is not None:
+            raise ValueError("valid must be None with uint16 ground truth (the blue sample is the validity)")
+    elif gt.dtype == torch.float32:
+        kind, want = 0, (n, 2, Hs, Ws)
+        if valid is not None:
+            if valid.dtype == torch.bool:
+                valid = valid.view(torch.uint8)
+            if valid.dtype != torch.uint8 or tuple(valid.shape) != (n, Hs, Ws) or valid.device != dev or not valid.is_contiguous():
+                raise ValueError("valid must be a contiguous bool / uint8 %s tensor on %s" % ((n, Hs, Ws), dev))
+    else:
+        raise ValueError("gt must be torch.uint16 [n,Hs,Ws,3] or float32 [n,2,Hs,Ws], got %s" % gt.dtype)
+    if tuple(gt.shape) != want or gt.device != dev or not gt.is_contiguous():
+        raise ValueError("gt must be contiguous %s %s on %s, got %s on %s" % (gt.dtype, want, dev, tuple(gt.shape), gt.device))
+    if params.dtype != torch.uint8 or tuple(params.shape) != (n, AUGMENT_RECORD_BYTES) or params.device != dev or not params.is_contiguous():
+        raise ValueError("params must be contiguous uint8 %s on %s" % ((n, AUGMENT_RECORD_BYTES), dev))
+    o = out if out is not None else (None, None, None)
+    if len(o) != 3:
+        raise ValueError("out must be (x, flow, valid)")
+    x = _out_arg(o[0], (n, 6, ch, cw), torch.float32, dev, contiguous=True)
+    flow = _out_arg(o[1], (n, 2, ch, cw), torch.float32, dev, contiguous=True)
+    vout = _out_arg(o[2], (n, 1, ch, cw), torch.float32, dev, contiguous=True)
+    status = _out_arg(status, (n,), torch.int32, dev, contiguous=True)
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_kitti_augment(frames.data_ptr(), gt.data_ptr(), kind, _ptr(valid), n, Hs, Ws, ch, cw, params.data_ptr(),
+                                           x.data_ptr(), flow.data_ptr(), vout.data_ptr(), status.data_ptr(), _stream(frames))
+    check(rc, "pwc_kitti_augment")
+    return x, flow, vout, status
 
 
 def lattice_unsplit(x: torch.Tensor, batch: int, levels: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
