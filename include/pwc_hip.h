@@ -36,6 +36,8 @@
  *                       (vectors, tips and flags; drawing stays with the caller)
  *   pwc_kitti_augment   KittiFlowDataset.__getitem__ data_processing_or.py:228-294 (reduced augmentation with cv2.warpAffine, random
  *                       crop, horizontal flip) from the raw uint8 frames and the ground truth, only the cropped window computed
+ *   pwc_kitti_augment_full   KittiAugmentationPipeline data_processing.py:136-279 (train2.py's collate_fn: crop, flip, rotation,
+ *                       translation, brightness / contrast, Gaussian blur) from the same raw inputs
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -600,6 +602,72 @@ typedef struct pwc_augment_params {
 int pwc_kitti_augment(const void *frames, const void *gt, int gt_kind, const void *valid /* may be NULL */, int n, int Hs, int Ws,
                       int crop_h, int crop_w, const void *params /* device pwc_augment_params [n] */, void *x, void *flow,
                       void *valid_out, void *status /* int32 [n] */, void *stream);
+
+/* Training batches of train2.py on the device (addition within ABI v13, csrc/pwc_augment_full.hip): KittiAugmentationPipeline
+ * (data_processing.py:136-279) -- random crop, horizontal flip, rotation up to +-17 degrees, integer translation, brightness /
+ * contrast, Gaussian blur, /255 -- in one launch.  frames, gt, gt_kind, valid, the slot layout with the sample's own row stride, the
+ * PNG decode and "valid == NULL -> all ones" are exactly those of pwc_kitti_augment above.  Outputs, all dense: x float
+ * [n][6][crop_h][crop_w], flow float [n][2][crop_h][crop_w], mask_out float [n][1][crop_h][crop_w] -- FRACTIONAL after a rotation, the
+ * reference does not threshold it again -- and status int32 [n].
+ *
+ * cv2 is DEFINED here by restatement, and parity against an actual cv2 build is UNPINNED in each of these points:
+ *   cv2.warpAffine (INTER_LINEAR, BORDER_REFLECT) of float32 images: OpenCV's classic fixed-point coordinates (as above) and the
+ *     float blend below;                                      parity against an actual cv2 build is unpinned
+ *   cv2.getRotationMatrix2D(center, angle, 1.0) in float64;   parity against an actual cv2 build is unpinned
+ *   cv2.GaussianBlur of 8U images: OpenCV's bit-exact fixed-point path (Q8.8 weights, uint16 horizontal pass, uint32 vertical pass,
+ *     BORDER_REFLECT_101);                                    parity against an actual cv2 build is unpinned
+ *   the Q8.8 weights are rounded from a FLOAT64 Gaussian, OpenCV computes it in softdouble: a stated, unpinned difference
+ *   the flow rotation is float64 because cos / sin are NumPy float64 scalars, which promote the float32 planes UNDER NUMPY 2
+ *     (checked on 2.2.6); under NumPy 1's value-based casting it would be float32: unpinned against other NumPy versions.
+ * Everything is integer arithmetic, or fp32 / fp64 in the expression order below without fused multiply-add: the result is
+ * bit-reproducible and bit-identical to tests/augment_full_oracle.py, which runs the stages in the reference's forward order.
+ *
+ * The reference crops FIRST: every later stage lives inside the crop_h x crop_w window, every border reflection is about the window's
+ * edges, and frame pixels outside the window are never read.  Two foldings of an integer p into [0, len), any number of reflections:
+ *   reflect(p, len)     BORDER_REFLECT      fedcba|abcdef|fedcba   m = p mod 2 len;      m < len ? m : 2 len - 1 - m
+ *   reflect101(p, len)  BORDER_REFLECT_101  fedcb|abcdef|edcba     m = p mod 2 (len-1);  m < len ? m : 2 (len-1) - m;  len == 1 -> 0
+ * One pwc_augment_full_params record (128 bytes, DEVICE buffer, 8-byte aligned) per sample:
+ *   m[6]    the INVERTED rotation matrix in fp64: M = [[al, be, (1-al) cx - be cy], [-be, al, be cx + (1-al) cy]] with
+ *           al = cos(angle pi/180), be = sin(angle pi/180), (cx, cy) = (crop_w / 2, crop_h / 2) in integer division, inverted as above
+ *   cs[2]   cos and sin of the angle in fp64 (applied to the flow vectors)
+ *   gain    (float)(brightness * contrast), the product taken in fp64
+ *   wk[7]   the ksize Q8.8 weights of the blur in wk[0 .. ksize), summing to exactly 256;  ksize 3, 5 or 7
+ *   y0, x0  crop origin;  h, w = H_b, W_b the sample's own size;  tx, ty the shift in pixels
+ *   flip, rot, trans, bright, blur   stage flags (non-zero = on); the fields of a stage that is off are ignored
+ * For output pixel (y, x) of the window the reference's stages are applied read-side, last stage first.  V(y, x) below is "the image
+ * values, the flow vector and the mask after stages 6..2 at window position (y, x)":
+ *   1 blur (images only):  s(j, i) = (uint8) trunc of the image value of V(reflect101(y + j, crop_h), reflect101(x + i, crop_w)),
+ *        |i|, |j| <= (ksize-1)/2;  out = (sum_j sum_i w_j w_i s(j, i) + 32768) >> 16;  x = (float)out / 255.f
+ *        (the horizontal sums fit uint16, the vertical uint32, nothing saturates because the weights add up to 256)
+ *     no blur:  x = value / 255.f on the float value -- values are quantised only when the blur is on
+ *   2 brightness / contrast (images only):  t = gain * (p - 127.5f) + 127.5f, each operation rounded to fp32;  p = min(max(t, 0), 255)
+ *   3 translation:  (y, x) <- (reflect(y - ty, crop_h), reflect(x - tx, crop_w)), an exact gather (through the fixed-point warp an
+ *        integer shift has fraction 0 and weights 1, 0, 0, 0)
+ *   4 rotation:  ad, bd, X0, Y0, Xq, Yq, sx, sy, fx, fy as for pwc_kitti_augment, with (Y, X) = (y, x) in WINDOW coordinates;
+ *        taps (ya, xa) = (reflect(sy, crop_h), reflect(sx, crop_w)), (yb, xb) = the same of sy + 1, sx + 1
+ *        gx = (float)fx / 32.f, gy alike;  w00 = (1-gy)*(1-gx), w01 = (1-gy)*gx, w10 = gy*(1-gx), w11 = gy*gx
+ *        every plane -- six image planes as (float)byte, u, v, mask:  f = ((p00*w00 + p01*w01) + p10*w10) + p11*w11
+ *        then  u' = (float)((double)u * cs[0] - (double)v * cs[1]);  v' = (float)((double)u' * cs[1] + (double)v * cs[0])
+ *        -- v' is computed from the ALREADY ROTATED u', as the reference does (its u is a view of the plane it has just overwritten)
+ *   5 flip:  every window tap column xt becomes crop_w - 1 - xt, and u of every tap is negated before it is blended
+ *   6 crop:  window tap (yt, xt) is pixel (y0 + yt, x0 + xt) of the sample
+ * A record the kernel cannot honour -- h not in [1, Hs], w not in [1, Ws], crop_h > h, crop_w > w, a crop origin outside
+ * [0, h-crop_h] x [0, w-crop_w], with blur on a ksize other than 3, 5, 7 or weights that do not add up to 256, with trans on |tx| or
+ * |ty| > PWC_AUGMENT_FULL_MAX_SHIFT -- never becomes a gather: that sample's outputs are zeros and status[b] = 1 (0 otherwise).  Every
+ * tap index is folded into the window whatever the matrix holds.  PWC_EINVAL / PWC_EALIGN, nothing launched: as pwc_kitti_augment. */
+#define PWC_AUGMENT_FULL_MAX_SHIFT 32767
+typedef struct pwc_augment_full_params {
+    double m[6];
+    double cs[2];
+    float gain;
+    uint16_t wk[7];
+    uint16_t ksize;
+    int32_t y0, x0, h, w, tx, ty;
+    int32_t flip, rot, trans, bright, blur;
+} pwc_augment_full_params;
+int pwc_kitti_augment_full(const void *frames, const void *gt, int gt_kind, const void *valid /* may be NULL */, int n, int Hs, int Ws,
+                           int crop_h, int crop_w, const void *params /* device pwc_augment_full_params [n] */, void *x, void *flow,
+                           void *mask_out, void *status /* int32 [n] */, void *stream);
 
 /* ---- fp16 convolution (first piece of the half-precision path, BASELINE configs 3-4) --------------------------
  * Activations are channel-blocked "c8": [B][ceil(C/8)][H][W][8] halves, channels past C zero; only the batch

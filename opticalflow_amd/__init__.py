@@ -9,5 +9,7 @@ from . import flowviz  # noqa: F401
 from .flowviz import dominant_direction, flow_to_color, quiver_arrows  # noqa: F401
 from . import augment  # noqa: F401
 from .augment import DeviceAugmenter, augment_batch  # noqa: F401
+from . import augment_full  # noqa: F401
+from .augment_full import DeviceFullAugmenter, augment_full_batch  # noqa: F401
 
 __version__ = "0.1.0"

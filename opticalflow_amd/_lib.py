@@ -110,6 +110,7 @@ SIGNATURES = {
     "pwc_flow_quiver": (c_int, [c_void_p] + [c_int] * 5 + [c_int64, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_float,
                                 c_void_p, c_int64, c_float] + [c_void_p] * 4),
     "pwc_kitti_augment": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 6),
+    "pwc_kitti_augment_full": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 6),
     "pwc_lattice_unsplit_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "pwc_conv2d_f16_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_uint, c_float, c_int64, c_int64, c_void_p]),

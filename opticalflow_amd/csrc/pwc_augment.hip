@@ -13,13 +13,11 @@
 // Bounds: a per-sample record is checked by the kernel before anything is read (the sample's outputs become zeros and status 1 when
 // it fails); with a record that passes, the warp == 0 read position lies in [0, h) x [0, w) by the crop-origin check and every
 // warped tap index is folded into [0, len) by reflect101 whatever the matrix holds, so no record can become an out-of-bounds gather.
-#include "pwc_common.h"
+#include "pwc_augment_taps.h"
 
 namespace {
 
-constexpr int kTH = 8, kTW = 128, kPix = 4, kThreads = 256;
-constexpr int kLanesX = kTW / kPix;            // 32 lanes across a tile row
-static_assert(kLanesX * kTH == kThreads, "augment tile");
+using namespace pwc_aug;
 static_assert(sizeof(pwc_augment_params) == 88, "augment parameter record");
 
 struct Args {
@@ -31,52 +29,6 @@ struct Args {
     int *status;
     int Hs, Ws, crop_h, crop_w, gt_kind;
 };
-
-// BORDER_REFLECT_101 for any p: period 2(len-1), len == 1 -> 0
-__device__ __forceinline__ int reflect101(int p, int len) {
-    if (len == 1) return 0;
-    const int period = 2 * (len - 1);
-    int m = p % period;
-    if (m < 0) m += period;
-    return m < len ? m : period - m;
-}
-
-// saturate_cast<int>(double): round half to even; out-of-range values saturate and NaN becomes INT_MIN (never undefined)
-__device__ __forceinline__ int round_i32(double v) {
-    return (int)fmin(fmax(rint(v), -2147483648.0), 2147483647.0);
-}
-
-__device__ __forceinline__ int wrap_add(int a, int b) { return (int)((unsigned)a + (unsigned)b); }
-
-// ground truth of one sample: (u, v, valid) at element `o` of the sample's slot
-struct Gt {
-    const float *fu, *fv;
-    const uint8_t *valid;
-    const uint16_t *png;
-    __device__ __forceinline__ void tap(int o, float &u, float &v, float &m) const {
-        if (png) {
-            const uint16_t *p = png + 3 * (int64_t)o;
-            u = ((float)p[0] - 32768.0f) / 64.0f;
-            v = ((float)p[1] - 32768.0f) / 64.0f;
-            m = p[2] != 0 ? 1.0f : 0.0f;
-        } else {
-            u = fu[o];
-            v = fv[o];
-            m = (!valid || valid[o] != 0) ? 1.0f : 0.0f;
-        }
-    }
-};
-
-template <bool VEC>
-__device__ __forceinline__ void store_row(float *__restrict__ row, int x0, int crop_w, const float (&v)[kPix]) {
-    if (VEC) {
-        *reinterpret_cast<float4 *>(row + x0) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < kPix; ++k)
-            if (x0 + k < crop_w) row[x0 + k] = v[k];
-    }
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kThreads) void kitti_augment_kernel(Args a) {

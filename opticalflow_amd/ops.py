@@ -658,17 +658,12 @@ def flow_quiver(flow: torch.Tensor, frame_h: int, frame_w: int, step: int, vec_s
 
 
 AUGMENT_RECORD_BYTES = 88      # sizeof(pwc_augment_params): six fp64, four fp32, six int32
+AUGMENT_FULL_RECORD_BYTES = 128     # sizeof(pwc_augment_full_params): eight fp64, one fp32, eight uint16, eleven int32
+AUGMENT_FULL_MAX_SHIFT = 32767      # PWC_AUGMENT_FULL_MAX_SHIFT
 
 
-def kitti_augment(frames: torch.Tensor, gt: torch.Tensor, params: torch.Tensor, crop_hw: Tuple[int, int],
-                  valid: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
-                  status: Optional[torch.Tensor] = None):
-    """(x float32 [n,6,ch,cw], flow float32 [n,2,ch,cw], valid float32 [n,1,ch,cw], status int32 [n]) of pwc_kitti_augment: the reduced
-    augmentation, crop and flip of KittiFlowDataset in one launch.  frames: uint8 [n,2,Hs,Ws,3] slots; gt: torch.uint16 [n,Hs,Ws,3]
-    (the KITTI PNG samples, `valid` must be None) or float32 [n,2,Hs,Ws] with `valid` None / bool or uint8 [n,Hs,Ws]; sample b lies
-    densely at the start of each of its slots with its own row stride W_b.  params: uint8 [n,88] device records (pwc_augment_params;
-    opticalflow_amd.augment builds and validates them).  status[b] != 0 marks a record the kernel refused (that sample's outputs are
-    zeros).  Device tensors only, no host synchronisation, bit-reproducible."""
+def _kitti_augment_call(symbol: str, record_bytes: int, frames, gt, params, crop_hw, valid, out, status):
+    """The argument checks and the call shared by pwc_kitti_augment and pwc_kitti_augment_full (one signature, one slot layout)."""
     if frames.dim() != 5 or frames.shape[1] != 2 or frames.shape[4] != 3 or frames.dtype != torch.uint8 or not frames.is_contiguous():
         raise ValueError("frames must be contiguous uint8 [n,2,Hs,Ws,3], got %s %s" % (frames.dtype, tuple(frames.shape)))
     _require_device(frames, "frames")
@@ -692,8 +687,8 @@ def kitti_augment(frames: torch.Tensor, gt: torch.Tensor, params: torch.Tensor, 
         raise ValueError("gt must be torch.uint16 [n,Hs,Ws,3] or float32 [n,2,Hs,Ws], got %s" % gt.dtype)
     if tuple(gt.shape) != want or gt.device != dev or not gt.is_contiguous():
         raise ValueError("gt must be contiguous %s %s on %s, got %s on %s" % (gt.dtype, want, dev, tuple(gt.shape), gt.device))
-    if params.dtype != torch.uint8 or tuple(params.shape) != (n, AUGMENT_RECORD_BYTES) or params.device != dev or not params.is_contiguous():
-        raise ValueError("params must be contiguous uint8 %s on %s" % ((n, AUGMENT_RECORD_BYTES), dev))
+    if params.dtype != torch.uint8 or tuple(params.shape) != (n, record_bytes) or params.device != dev or not params.is_contiguous():
+        raise ValueError("params must be contiguous uint8 %s on %s" % ((n, record_bytes), dev))
     o = out if out is not None else (None, None, None)
     if len(o) != 3:
         raise ValueError("out must be (x, flow, valid)")
@@ -702,10 +697,33 @@ def kitti_augment(frames: torch.Tensor, gt: torch.Tensor, params: torch.Tensor, 
     vout = _out_arg(o[2], (n, 1, ch, cw), torch.float32, dev, contiguous=True)
     status = _out_arg(status, (n,), torch.int32, dev, contiguous=True)
     with torch.cuda.device(dev):
-        rc = _lib.load().pwc_kitti_augment(frames.data_ptr(), gt.data_ptr(), kind, _ptr(valid), n, Hs, Ws, ch, cw, params.data_ptr(),
-                                           x.data_ptr(), flow.data_ptr(), vout.data_ptr(), status.data_ptr(), _stream(frames))
-    check(rc, "pwc_kitti_augment")
+        rc = getattr(_lib.load(), symbol)(frames.data_ptr(), gt.data_ptr(), kind, _ptr(valid), n, Hs, Ws, ch, cw, params.data_ptr(),
+                                          x.data_ptr(), flow.data_ptr(), vout.data_ptr(), status.data_ptr(), _stream(frames))
+    check(rc, symbol)
     return x, flow, vout, status
+
+
+def kitti_augment(frames: torch.Tensor, gt: torch.Tensor, params: torch.Tensor, crop_hw: Tuple[int, int],
+                  valid: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                  status: Optional[torch.Tensor] = None):
+    """(x float32 [n,6,ch,cw], flow float32 [n,2,ch,cw], valid float32 [n,1,ch,cw], status int32 [n]) of pwc_kitti_augment: the reduced
+    augmentation, crop and flip of KittiFlowDataset in one launch.  frames: uint8 [n,2,Hs,Ws,3] slots; gt: torch.uint16 [n,Hs,Ws,3]
+    (the KITTI PNG samples, `valid` must be None) or float32 [n,2,Hs,Ws] with `valid` None / bool or uint8 [n,Hs,Ws]; sample b lies
+    densely at the start of each of its slots with its own row stride W_b.  params: uint8 [n,88] device records (pwc_augment_params;
+    opticalflow_amd.augment builds and validates them).  status[b] != 0 marks a record the kernel refused (that sample's outputs are
+    zeros).  Device tensors only, no host synchronisation, bit-reproducible."""
+    return _kitti_augment_call("pwc_kitti_augment", AUGMENT_RECORD_BYTES, frames, gt, params, crop_hw, valid, out, status)
+
+
+def kitti_augment_full(frames: torch.Tensor, gt: torch.Tensor, params: torch.Tensor, crop_hw: Tuple[int, int],
+                       valid: Optional[torch.Tensor] = None, out: Optional[Tuple[torch.Tensor, torch.Tensor, torch.Tensor]] = None,
+                       status: Optional[torch.Tensor] = None):
+    """(x float32 [n,6,ch,cw], flow float32 [n,2,ch,cw], mask float32 [n,1,ch,cw] -- fractional after a rotation --, status int32 [n]) of
+    pwc_kitti_augment_full: train2.py's KittiAugmentationPipeline (crop, flip, rotation, translation, brightness / contrast, Gaussian
+    blur) in one launch.  frames / gt / valid: the slot tensors of kitti_augment.  params: uint8 [n,128] device records
+    (pwc_augment_full_params; opticalflow_amd.augment_full builds and validates them).  status[b] != 0 marks a record the kernel refused
+    (that sample's outputs are zeros).  Device tensors only, no host synchronisation, bit-reproducible."""
+    return _kitti_augment_call("pwc_kitti_augment_full", AUGMENT_FULL_RECORD_BYTES, frames, gt, params, crop_hw, valid, out, status)
 
 
 def lattice_unsplit(x: torch.Tensor, batch: int, levels: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
