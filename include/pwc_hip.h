@@ -123,9 +123,12 @@ const char *pwc_last_error(void);
  * Unknown name: PWC_EINVAL.  A captured HIP graph keeps the kernels chosen at capture time. */
 int pwc_set_option(const char *name, int value);
 int pwc_get_option(const char *name, int *value);
-/* Name and template arguments of the MFMA convolution variant this thread launched last -- what the tile cost
- * model picked for that layer: "conv3x3_mfma_kernel<MT, NT, stride, dilation, two-per-CU, 0>" (fp32) or
- * "conv3x3_f16_kernel<MT, NT, stride, dilation, ring, 0>" (fp16).  For benchmarks and profiles. */
+/* Name and template arguments of the convolution kernel this thread launched last -- what the tile cost
+ * model picked for that layer: "conv3x3_mfma_kernel<MT, NT, stride, dilation, two-per-CU, 0 | 16 = folded tile>" (fp32) or
+ * "conv3x3_f16_kernel<MT, NT, stride, dilation, ring, 0>" (fp16).  Every fp32 3x3 path leaves its name: the split-K form
+ * ("conv3x3_mfma_splitk_kernel<1, 1, stride, dilation, 0, fold>"), the 16-cout kernel ("conv3x3_mfma16_kernel<NT, CK, ...>"), the
+ * 2-channel heads ("stream3x3_kernel<mode, TH, KS, sliced, ...>", "conv3x3_head_kernel<2, ...>"), the Winograd kernels.
+ * For benchmarks, profiles and the launch audits. */
 const char *pwc_last_conv_kernel(void);
 
 /* Cost volume.  in1,in2: [B,C,H,W]; out: [B,(2*(max_disp/stride2)+1)^2,outH,outW] with

@@ -108,6 +108,7 @@ int run_head(const float *x, const float *w_raw, const float *bias, const float 
     if (nblk > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv2d_fwd: grid too large");
     hipLaunchKernelGGL((conv3x3_head_kernel<2>), dim3((unsigned)nblk), dim3(kHThreads), 0, st,
                        x, w_raw, bias, residual, y, Cin, H, W, tiles_x, tiles_y, bsx, bsy, bsr, slope, do_leaky);
+    pwc::note_kernel("conv3x3_head_kernel", 2, 0, 0, 0, 0, 0);
     return pwc::check_launch("conv3x3_head_kernel");
 }
 

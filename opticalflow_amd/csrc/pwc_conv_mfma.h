@@ -483,6 +483,7 @@ int launch_split(const ConvArgs &a) {
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)groups, (unsigned)a.ksplit), dim3(kThreads), G::kSmemBytes,
                        a.stream, a.x, a.wp, a.bias, (const float *)nullptr, a.partial, a.Cin, a.H, a.W, a.Cout, a.CoutP,
                        a.Ho, a.Wo, tiles_x, tiles_y, a.bsx, bsp, (int64_t)0, 0.f, 0, a.cps, (int64_t)a.B * bsp, a.p16());
+    pwc::note_kernel("conv3x3_mfma_splitk_kernel", 1, 1, S, D, 0, FOLD ? 16 : 0);    // the SPLIT form of <1, 1, S, D, 0>: raw partial sums
     return pwc::check_launch("conv3x3_mfma_kernel<split>");
 }
 
@@ -504,6 +505,7 @@ int launch16(const ConvArgs &a) {
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(kThreads), G::kSmemBytes, a.stream,
                        a.x, a.wp, a.bias, a.residual, a.y, a.Cin, a.H, a.W, a.Cout, a.CoutP, tiles_x, tiles_y,
                        a.bsx, a.bsy, a.bsr, a.slope, a.do_leaky, a.p16());
+    pwc::note_kernel("conv3x3_mfma16_kernel", NT, CKT, 1, 1, 0, 0);
     return pwc::check_launch("conv3x3_mfma16_kernel");
 }
 

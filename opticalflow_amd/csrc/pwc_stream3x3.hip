@@ -436,6 +436,7 @@ int launch_cfg(const float *x, int B, int Cin, int H, int W, int64_t bsx,
     hipLaunchKernelGGL(kern, dim3((unsigned)nblk), dim3(G::kBlockThreads), smem, st,
                        x, Cin, H, W, tiles_x, tiles_y, bsx, hw, hbias, residual, hy, bshy, bsr, slope, do_leaky,
                        uw, ubias, uy, bsuy, nslice, cslice);
+    pwc::note_kernel("stream3x3_kernel", MODE, TH, KS, nslice > 1 ? 1 : 0, 0, 0);     // (fourth field: 1 = Cin slices through the workspace)
     return pwc::check_launch("stream3x3_kernel");
 }
 

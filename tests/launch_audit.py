@@ -12,6 +12,11 @@ built with -ffp-contract=off and IEEE division), restated here in float32 torch 
 the mask decisions agree exactly; pixels whose float64 mask sum lies within 1e-6 of the threshold are still counted and left out.
 
 Route labels come from the same public queries the plan uses (*_preferred, *_workspace_bytes, _lib.get_option, tile counts).
+Every convolution record also keeps the kernel instantiation the library launched (pwc_last_conv_kernel, read right after the
+launch: name and template arguments, "/split" where the launch went through the split workspace), as tests/launch_audit_f16.py does.
+The 16 -> 16 Winograd launches of the first pyramid level are checked too: one layer like any F(2x2) launch; the two-layer launch
+against the float64 composition under  REL_WINO2 x (sum |w2| S1 + S2),  S1 the first layer's sum of |terms| (its error, bounded by
+REL_WINO2 x S1, passes LeakyReLU with slope <= 1 and is weighted by |w2|) and S2 the second layer's over the float64 intermediate.
 This module is a helper, not a test module (tests/f16_error_budget.py is the precedent)."""
 from __future__ import annotations
 
@@ -45,10 +50,153 @@ ROUTES_REQUIRED = (
     "head/head10", "head/upsample-entry", "head/upfeat", "head/upfeat-sliced", "head/conv", "deconv",
     "entry/fused-window", "entry/fused-r2", "entry/warp", "entry/corr-small", "entry/corr-level6",
     "ctx/lattice-unsplit",
+    "pyr1/wino2",
 )
 
-OPS = ("densify", "conv3x3", "conv3x3_wino", "conv3x3_wino4", "warp_correlation", "warp", "correlation", "head_upfeat",
-       "upsample_entry", "deconv4x4s2", "lattice_unsplit")
+# ---- kernel instantiations the suite must launch (test_kernel_coverage) ---------------------------------------------------------------
+# Every label the fp32 plan produced on the census grid (plan_census.grid(), default options) and at 448x1024 with batch 1, 2, 4, 8, 16
+# and 32, as tools/kernel_census.py collected them on an MI355X (profiles/kernel_census_fp32.json, "grid_union").  A label is what
+# pwc_last_conv_kernel reports after the launch -- for a layer the library runs as two launches (F(4x4): a 64-cout and a 32-cout one)
+# the LAST of them -- plus "/split" where the layer went through the split workspace.  conv3x3_mfma_kernel<MT, NT, stride, dilation,
+# two per CU, 16 = folded tile>, conv3x3_wino4p_kernel<CB, TG, GW, Cin slices, 1, IH>, conv3x3_wino8r_kernel<MT, TG, 1, dilation, 1, 0>
+KERNELS_REQUIRED = (
+    "conv3x3_head_kernel<2, 0, 0, 0, 0, 0>",
+    "conv3x3_mfma16_kernel<1, 4, 1, 1, 0, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 1, 0, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 1, 1, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 1, 1, 16>",
+    "conv3x3_mfma_kernel<1, 1, 1, 16, 0, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 16, 1, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 2, 0, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 2, 1, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 4, 0, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 4, 1, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 8, 0, 0>",
+    "conv3x3_mfma_kernel<1, 1, 1, 8, 1, 0>",
+    "conv3x3_mfma_kernel<1, 1, 2, 1, 0, 0>",
+    "conv3x3_mfma_kernel<1, 1, 2, 1, 1, 0>",
+    "conv3x3_mfma_kernel<1, 1, 2, 1, 1, 16>",
+    "conv3x3_mfma_kernel<1, 2, 1, 4, 1, 0>",
+    "conv3x3_mfma_kernel<1, 2, 1, 8, 1, 0>",
+    "conv3x3_mfma_kernel<1, 2, 2, 1, 1, 0>",
+    "conv3x3_mfma_kernel<2, 1, 1, 2, 1, 0>",
+    "conv3x3_mfma_kernel<2, 1, 1, 4, 1, 0>",
+    "conv3x3_mfma_kernel<2, 1, 2, 1, 1, 0>",
+    "conv3x3_mfma_kernel<2, 2, 2, 1, 1, 0>",
+    "conv3x3_mfma_kernel<3, 1, 1, 1, 1, 0>",
+    "conv3x3_mfma_kernel<3, 1, 2, 1, 1, 0>",
+    "conv3x3_mfma_kernel<3, 2, 2, 1, 1, 0>",
+    "conv3x3_mfma_splitk_kernel<1, 1, 1, 1, 0, 0>/split",
+    "conv3x3_mfma_splitk_kernel<1, 1, 1, 1, 0, 16>/split",
+    "conv3x3_wino4p_kernel<2, 4, 32, 1, 1, 16>",
+    "conv3x3_wino4p_kernel<2, 4, 32, 2, 1, 16>/split",
+    "conv3x3_wino4p_kernel<2, 4, 32, 4, 1, 16>/split",
+    "conv3x3_wino4p_kernel<2, 4, 32, 8, 1, 0>/split",
+    "conv3x3_wino4p_kernel<2, 4, 64, 1, 1, 0>",
+    "conv3x3_wino4p_kernel<2, 4, 64, 1, 1, 0>/split",
+    "conv3x3_wino4p_kernel<2, 4, 64, 2, 1, 0>/split",
+    "conv3x3_wino4p_kernel<2, 4, 64, 4, 1, 0>/split",
+    "conv3x3_wino4p_kernel<2, 4, 64, 7, 1, 0>/split",
+    "conv3x3_wino4p_kernel<2, 4, 64, 8, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 16, 1, 1, 8>",
+    "conv3x3_wino4p_kernel<4, 2, 16, 2, 1, 8>/split",
+    "conv3x3_wino4p_kernel<4, 2, 16, 4, 1, 8>/split",
+    "conv3x3_wino4p_kernel<4, 2, 32, 2, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 32, 3, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 32, 4, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 32, 5, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 32, 6, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 32, 7, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 32, 8, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 1, 1, 0>",
+    "conv3x3_wino4p_kernel<4, 2, 64, 1, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 2, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 3, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 4, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 5, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 6, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 7, 1, 0>/split",
+    "conv3x3_wino4p_kernel<4, 2, 64, 8, 1, 0>/split",
+    "conv3x3_wino8r_kernel<1, 4, 1, 1, 1, 0>",
+    "conv3x3_wino8r_kernel<1, 4, 1, 1, 1, 0>/split",
+    "conv3x3_wino8r_kernel<2, 2, 1, 1, 1, 0>",
+    "conv3x3_wino8r_kernel<2, 2, 1, 1, 1, 0>/split",
+    "conv3x3_wino8r_kernel<4, 1, 1, 1, 1, 0>",
+    "conv3x3_wino8r_kernel<4, 1, 1, 1, 1, 0>/split",
+    "conv3x3_wino8r_kernel<4, 1, 1, 2, 1, 0>",
+    "conv3x3_wino8r_kernel<4, 1, 1, 4, 1, 0>",
+    "image_conv_s2_f32_kernel<1, 2, 2, 1, 0, 0>",
+    "pyr1_wino2<8, 64, 0, 0, 0, 0>",
+    "stream3x3_kernel<1, 4, 4, 0, 0, 0>",
+    "stream3x3_kernel<1, 4, 4, 1, 0, 0>/split",
+    "stream3x3_kernel<1, 8, 1, 0, 0, 0>",
+    "stream3x3_kernel<3, 4, 4, 0, 0, 0>",
+    "stream3x3_kernel<3, 4, 4, 1, 0, 0>",
+)
+
+OPS = ("densify", "conv3x3", "conv3x3_wino", "conv3x3_wino4", "pyr1_wino", "pyr1_wino_pair", "warp_correlation", "warp", "correlation",
+       "head_upfeat", "upsample_entry", "deconv4x4s2", "lattice_unsplit")
+
+
+def last_kernel(split: bool = False) -> str:
+    """the convolution kernel the library launched last on this thread: name<template arguments>[/split]"""
+    from opticalflow_amd import _lib
+    return _lib.load().pwc_last_conv_kernel().decode() + ("/split" if split else "")
+
+
+CONV_OPS = ("conv3x3", "conv3x3_wino", "conv3x3_wino4", "pyr1_wino", "pyr1_wino_pair", "head_upfeat")
+
+
+def split_need(op: str, A: Dict) -> int:
+    """bytes of split workspace the launch `op`(**A) wants (0: it does not split; the pyramid kernels never do)"""
+    from opticalflow_amd import ops
+    if op not in ("conv3x3", "conv3x3_wino", "conv3x3_wino4"):
+        return 0
+    n, cin, h, w = A["x"].shape
+    if op == "conv3x3":
+        return ops.conv3x3_workspace_bytes(n, cin, h, w, A["cout"], A["stride"], A["dilation"])
+    if op == "conv3x3_wino":
+        return ops.conv3x3_wino_workspace_bytes(n, cin, h, w, A["cout"], A["dilation"])
+    return ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, A["cout"])
+
+
+def used_split(op: str, A: Dict) -> bool:
+    """did the launch go through the split workspace?  (every C entry splits when the buffer it is given covers its demand)"""
+    ws, need = A.get("workspace"), split_need(op, A)
+    return bool(ws is not None and 0 < need <= ws.numel() * ws.element_size())
+
+
+class KernelSpy:
+    """Context manager: wraps the convolution operators of opticalflow_amd.ops, launches them unchanged and collects the kernel
+    label of each (`kernels`), with no reference and no synchronisation -- tools/kernel_census.py runs hundreds of forwards under it."""
+
+    def __init__(self):
+        self.kernels = set()
+        self._real = {}
+
+    def __enter__(self):
+        from opticalflow_amd import ops
+        for n in CONV_OPS:
+            self._real[n] = getattr(ops, n)
+            setattr(ops, n, self._wrap(n, self._real[n]))
+        return self
+
+    def __exit__(self, *exc):
+        from opticalflow_amd import ops
+        for n, f in self._real.items():
+            setattr(ops, n, f)
+        return False
+
+    def _wrap(self, name, real):
+        sig = inspect.signature(real)
+
+        def f(*a, **kw):
+            ba = sig.bind(*a, **kw)
+            ba.apply_defaults()
+            out = real(*a, **kw)
+            self.kernels.add(last_kernel(used_split(name, ba.arguments)))
+            return out
+        return f
 
 
 def pick_images(n: int, seed: int) -> List[int]:
@@ -185,7 +333,7 @@ def near_threshold(taps, thr: float) -> torch.Tensor:
 # ---- the spies ---------------------------------------------------------------------------------------------------------------------
 class LaunchAudit:
     """Install with `install(monkeypatch, plan)`, run plan.run(x) (eager), then read `records` / `routes`.  Every record:
-    {op, route, shape, images, ratio (max error / bound over the checked elements), excluded, pixels}."""
+    {op, route, kernel (convolutions; else ""), shape, images, ratio (max error / bound over the checked elements), excluded, pixels}."""
 
     def __init__(self, seed: int = 0):
         self.records: List[Dict] = []
@@ -196,6 +344,10 @@ class LaunchAudit:
     @property
     def routes(self):
         return {r["route"] for r in self.records}
+
+    @property
+    def kernels(self):
+        return {r["kernel"] for r in self.records if r["kernel"]}
 
     def worst_by_family(self) -> Dict[str, float]:
         out: Dict[str, float] = {}
@@ -210,7 +362,7 @@ class LaunchAudit:
     # raw filter bank of a packed buffer (the plan keeps both)
     def _raw_weight(self, packed: torch.Tensor) -> torch.Tensor:
         p = self.plan
-        for d in (p.packed, p.wino_packed, p.wino4_packed):
+        for d in (p.packed, p.wino_packed, p.wino4_packed, p.pyr1_packed):
             for k, t in d.items():
                 if t.data_ptr() == packed.data_ptr() and t.numel() == packed.numel():
                     base, sl = (k.split("[", 1) + [""])[:2]
@@ -222,9 +374,9 @@ class LaunchAudit:
                     return w.detach().float().cpu()
         raise KeyError("packed weights not held by the plan")
 
-    def _record(self, op, route, shape, images, ratio, excluded=0, pixels=0):
-        self.records.append(dict(op=op, route=route, shape=tuple(shape), images=images, ratio=float(ratio), excluded=int(excluded),
-                                 pixels=int(pixels)))
+    def _record(self, op, route, shape, images, ratio, excluded=0, pixels=0, kernel=""):
+        self.records.append(dict(op=op, route=route, kernel=kernel, shape=tuple(shape), images=images, ratio=float(ratio),
+                                 excluded=int(excluded), pixels=int(pixels)))
 
     def install(self, monkeypatch, plan) -> None:
         from opticalflow_amd import engine, ops
@@ -272,6 +424,7 @@ class LaunchAudit:
         w = self._raw_weight(wp)
         b = bias.detach().float().cpu()
         out = real(**A)
+        kernel = last_kernel(used_split(op, A))
         torch.cuda.synchronize()
         if split2_out:
             got = torch.cat([out[4 * i:4 * i + 4] for i in imgs]).cpu()
@@ -280,7 +433,7 @@ class LaunchAudit:
         ref, s = conv_ref(xs, w, b, stride, dilation, A["leaky_slope"] is not None, rs)
         if split2_out:
             ref, s = split2(ref), split2(s)
-        self._record(op, route, x.shape, len(imgs), worst(bounded_ratio(got, ref, s, rel))[0])
+        self._record(op, route, x.shape, len(imgs), worst(bounded_ratio(got, ref, s, rel))[0], kernel=kernel)
         return out
 
     def _check_conv3x3(self, real, A):
@@ -288,6 +441,7 @@ class LaunchAudit:
         x, cout = A["x"], A["cout"]
         n, cin, h, w = x.shape
         s, d = A["stride"], A["dilation"]
+        need = ops.conv3x3_workspace_bytes(n, cin, h, w, cout, s, d)
         if s == 2:
             route = "conv/direct/s2"
         elif A["residual"] is not None:
@@ -298,7 +452,7 @@ class LaunchAudit:
             route = "head/conv"
         elif d > 1:
             route = "conv/direct/dilated"
-        elif A["workspace"] is not None and 0 < ops.conv3x3_workspace_bytes(n, cin, h, w, cout, s, d):
+        elif A["workspace"] is not None and 0 < need:
             route = "conv/direct/split-k"
         else:
             route = "conv/direct"
@@ -309,11 +463,12 @@ class LaunchAudit:
         from opticalflow_amd import ops
         x, cout, d = A["x"], A["cout"], A["dilation"]
         n, cin, h, w = x.shape
+        need = ops.conv3x3_wino_workspace_bytes(n, cin, h, w, cout, d)
         if self.in_split96:
             route = "conv/split96/wino2"
         elif d > 1:
             route = "conv/wino2/dilated"
-        elif A["workspace"] is not None and 0 < ops.conv3x3_wino_workspace_bytes(n, cin, h, w, cout, d):
+        elif A["workspace"] is not None and 0 < need:
             route = "conv/wino2/split-k"
         else:
             route = "conv/wino2"
@@ -323,15 +478,36 @@ class LaunchAudit:
         from opticalflow_amd import ops
         x, cout = A["x"], A["cout"]
         n, cin, h, w = x.shape
+        need = ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, cout)
         if self.in_split96:
             route = "conv/split96/wino4"
         elif A["split2"]:
             route = "conv/wino4/split2"
-        elif A["workspace"] is not None and 0 < ops.conv3x3_wino4_workspace_bytes(n, cin, h, w, cout):
+        elif A["workspace"] is not None and 0 < need:
             route = "conv/wino4/cin-split"
         else:
             route = "conv/wino4"
         return self._conv_common("conv3x3_wino4", real, A, route, REL_WINO4, 1, 1, split2_out=A["split2"])
+
+    def _check_pyr1_wino(self, real, A):
+        return self._conv_common("pyr1_wino", real, A, "pyr1/wino2", REL_WINO2)
+
+    def _check_pyr1_wino_pair(self, real, A):
+        x = A["x"]
+        imgs = pick_images(x.shape[0], self.seed + len(self.records))
+        xs = x[imgs].cpu()
+        w1, w2 = self._raw_weight(A["upacked1"]), self._raw_weight(A["upacked2"])
+        b1, b2 = A["bias1"].detach().float().cpu(), A["bias2"].detach().float().cpu()
+        out = real(**A)
+        kernel = last_kernel()
+        torch.cuda.synchronize()
+        y1, s1 = conv_ref(xs, w1, b1)
+        ref = F.leaky_relu(F.conv2d(y1, w2.double(), b2.double(), padding=1), LEAKY)
+        s2 = F.conv2d(y1.abs(), w2.double().abs(), b2.double().abs(), padding=1)
+        s = F.conv2d(s1, w2.double().abs(), None, padding=1) + s2
+        self._record("pyr1_wino_pair", "pyr1/pair", x.shape, len(imgs), worst(bounded_ratio(out[imgs].cpu(), ref, s, REL_WINO2))[0],
+                     kernel=kernel)
+        return out
 
     def _check_head_upfeat(self, real, A):
         from opticalflow_amd import ops
@@ -345,12 +521,13 @@ class LaunchAudit:
         wf = self._raw_weight(A["head_wpacked"])
         bf, uw, ub = (A[k].detach().float().cpu() for k in ("head_bias", "up_weight", "up_bias"))
         real(**A)
+        kernel = last_kernel()
         torch.cuda.synchronize()
         gf, gu = A["flow_out"][imgs].cpu(), A["up_out"][imgs].cpu()
         rf, sf = conv_ref(xs, wf, bf, act=False)
         ru, su = deconv_ref(xs, uw, ub)
         r = max(worst(bounded_ratio(gf, rf, sf, REL_HEAD))[0], worst(bounded_ratio(gu, ru, su, REL_HEAD))[0])
-        self._record("head_upfeat", route, x.shape, len(imgs), r)
+        self._record("head_upfeat", route, x.shape, len(imgs), r, kernel=kernel)
 
     def _check_upsample_entry(self, real, A):
         head = A["head"]

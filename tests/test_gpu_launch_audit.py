@@ -1,7 +1,10 @@
 """Launch audit of the fp32 inference plan: every ops.* launch of one eager forward against a float64 CPU reference of that single
 operator, computed from the launch's own recorded inputs, with a per-element bound (tests/launch_audit.py), at the geometries and
 options that send layers to different kernel routes; then flow2 (and the training-mode tuple up to 256x512) end to end against the
-float64 oracle with a MAX per-pixel endpoint-error bound; then the union of routes reached against a fixed list.
+float64 oracle with a MAX per-pixel endpoint-error bound; then the union of routes reached against a fixed list, and the union of
+kernel instantiations launched against launch_audit.KERNELS_REQUIRED.  Each configuration's plan must also hold exactly the routing
+signatures the device-less census recorded for it (tests/plan_census.py, tests/golden/plan_census_configs.json):
+tests/test_plan_census_cpu.py proves on the CPU that those signatures cover every small geometry of its grid.
 
 The fp16 / fp16-strict plans have their own per-launch audit (tests/test_gpu_launch_audit_f16.py, tests/launch_audit_f16.py: half
 operands, fp32 accumulation, one rounding to half at the store); multi-GPU runs are outside both."""
@@ -11,6 +14,7 @@ import pytest
 import torch
 
 import launch_audit as LA
+import plan_census as PC
 from conftest import seeded_rand
 from oracle import pwc_oracle as O
 
@@ -42,9 +46,20 @@ CONFIGS = [
     ("b3-128x192", "dc", 3, 128, 192, None, "small maps, W not a power of two"),
     ("old-b2-256x512", "old", 2, 256, 512, None, "PWCDCNet_old: permuted filters through the same kernels"),
     ("opts-b2-256x512", "dc", 2, 256, 512, NON_DEFAULT, "non-default options: conv+deconv heads, round-2 fused kernel, unsplit F(4x4)"),
+    # small geometries chosen by greedy cover over the plan census (tests/test_plan_census_cpu.py)
+    ("b8-192x320", "dc", 8, 192, 320, None, "W/4 = 80: conv2_0..2 and dc_conv1 on unsplit F(2x2), conv2_3 on split-K F(2x2), conv2_4 and "
+                                            "conv3_0..2 on the direct kernel; level maps 80 .. 5 columns wide"),
+    ("b8-384x64", "dc", 8, 384, 64, None, "portrait strip, W/4 = 16: conv2_2 and dc_conv1 (Cin 565) on the direct kernel"),
+    ("b6-192x192", "dc", 6, 192, 192, None, "W/4 = 48: conv2_3 on the direct kernel"),
+    ("b8-320x192", "dc", 8, 320, 192, None, "portrait: conv2_3 on unsplit F(2x2)"),
+    # kernel instantiations no configuration above launches (tools/kernel_census.py, launch_audit.KERNELS_REQUIRED)
+    ("b7-128x384", "dc", 7, 128, 384, None, "F(4x4) whole-launch Cin splits in 3, 6 and 8 slices on 32-column tile groups"),
+    ("b5-128x256", "dc", 5, 128, 256, None, "F(4x4) in 5 slices on 64-column groups; the stacked 8x16 form in 4 slices"),
+    ("b7-128x256", "dc", 7, 128, 256, None, "the direct kernel's 96-cout tile <3, 1> at two workgroups per CU"),
 ]
 
 ROUTES_SEEN = {}
+KERNELS_SEEN = {}
 
 
 @pytest.fixture
@@ -97,10 +112,19 @@ def test_launch_audit(gpu_device, monkeypatch, all_options, cfg):
     monkeypatch.undo()
     t_audit = time.time() - t0
     ROUTES_SEEN[cid] = audit.routes
+    KERNELS_SEEN[cid] = audit.kernels
     worst = audit.worst_by_family()
     print("\n[%s] %d launches, %.1f s; worst error/bound per family: %s" % (
         cid, len(audit.records), t_audit, ", ".join("%s %.3f" % kv for kv in sorted(worst.items()))))
     print("[%s] routes: %s" % (cid, " ".join(sorted(audit.routes))))
+    print("[%s] kernels: %s" % (cid, " | ".join(sorted(audit.kernels))))
+    # the census (built without a device, 256 compute units assumed) must describe THIS plan, or its coverage proof is about another one
+    census = PC.load_config_census()[cid]
+    got_sigs, got_shape = PC.plan_signatures(plan), PC.plan_shape(plan)
+    cus = torch.cuda.get_device_properties(gpu_device).multi_processor_count
+    assert got_sigs == census[0] and got_shape == census[1], (
+        "the plan built on this device (%d compute units) differs from the census for %s (256 assumed): only on the device %s, only "
+        "in the census %s, shape %s vs %s" % (cus, cid, sorted(got_sigs - census[0]), sorted(census[0] - got_sigs), got_shape, census[1]))
     for r in audit.records:
         if r["pixels"]:
             assert r["excluded"] <= LA.MASK_EXCLUDED_MAX * r["pixels"], r
@@ -139,6 +163,17 @@ def test_route_coverage():
     union = set().union(*ROUTES_SEEN.values())
     print("\nroute union: %s" % " ".join(sorted(union)))
     assert set(LA.ROUTES_REQUIRED) <= union, sorted(set(LA.ROUTES_REQUIRED) - union)
+
+
+def test_kernel_coverage():
+    """every kernel instantiation named in launch_audit.KERNELS_REQUIRED -- what the plan launches anywhere on the census grid and at
+    the benchmark sizes (tools/kernel_census.py) -- was launched, and so checked per element, by the configurations above"""
+    missing_cfg = [c[0] for c in CONFIGS if c[0] not in KERNELS_SEEN]
+    if missing_cfg:
+        pytest.skip("needs the launch-audit configurations of this module in the same run (missing %s)" % missing_cfg)
+    union = set().union(*KERNELS_SEEN.values())
+    print("\nkernel union (%d): %s" % (len(union), " | ".join(sorted(union))))
+    assert set(LA.KERNELS_REQUIRED) <= union, sorted(set(LA.KERNELS_REQUIRED) - union)
 
 
 def test_comparator_reports_a_perturbed_bias_channel(gpu_device):

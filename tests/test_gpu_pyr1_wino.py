@@ -224,11 +224,11 @@ def test_forward_routes_agree(gpu_device, geom):
             _lib.set_option(n, v)
     old = res[0][1]
     print("level-1 kernels, option 0: %s" % old)
-    # option 0: the parent's five launches, all through pwc_conv2d_fwd (its 16-cout kernel leaves no name of its own: what is read back
-    # after conv1aa / conv1b is still conv1a's, as on the parent)
+    # option 0: five launches, all through pwc_conv2d_fwd; conv1aa / conv1b on its 16-cout kernel, which names itself (it used to leave
+    # conv1a's name standing: the launch audit records the kernel of every launch, so a stale name would be a wrong record)
     assert [t for t, _ in old] == ["conv3x3"] * 5 and all("pyr1" not in k for _, k in old)
     assert "image_conv_s2_f32" in old[0][1] and "image_conv_s2_f32" in old[1][1]
-    assert old[2][1] == old[1][1] and old[3][1] == old[1][1] and "conv3x3_mfma_kernel" in old[4][1]
+    assert "conv3x3_mfma16_kernel" in old[2][1] and old[3][1] == old[2][1] and "conv3x3_mfma_kernel" in old[4][1]
     new = res[1][1]
     print("level-1 kernels, option 1: %s" % new)
     assert [t for t, _ in new] == ["conv3x3", "conv3x3", "pyr1_wino", "pyr1_wino", "conv3x3"]
