@@ -26,6 +26,9 @@
 #pragma once
 #include <stdlib.h>
 
+#include <iterator>
+#include <utility>
+
 #include "pwc_common.h"
 
 // output store policy of the MFMA kernels: -DPWC_CONV_NT_STORE streams the activations past L2 (experiment)
@@ -86,7 +89,8 @@ struct Geom {
     static constexpr int kWRegion = kWSlots * kThreads * 4;                       // floats
     static constexpr int kBufFloats = kInRegion + kWRegion;
     static constexpr int kSmemBytes = 2 * kBufFloats * 4;
-    // does this variant exist?  TWO needs two workgroups' LDS and accumulators + operands within 256 registers
+    // does this variant fit (launch<> asserts it for every entry of the tile tables)?  TWO needs two workgroups' LDS and accumulators
+    // + operands within 256 registers
     static constexpr bool kValid = TWO ? (kSmemBytes <= 80 * 1024 && MT * NT <= 8)
                                        : (kSmemBytes <= 160 * 1024 && MT * NT <= 16);
 };
@@ -447,24 +451,21 @@ namespace {
 template <int MT, int NT, int S, int D, int TWO, int FOLD = 0>
 int launch(const ConvArgs &a) {
     using G = Geom<MT, NT, S, D, TWO, 0, FOLD>;
-    if constexpr (!G::kValid) {
-        PWC_FAIL(PWC_EINVAL, "pwc_conv2d_fwd: internal: tile %dx%d two=%d does not exist", MT, NT, TWO);
-    } else {
-        const int tiles_x = (a.Wo + G::kTW - 1) / G::kTW;
-        const int tiles_y = (a.Ho + G::kTileH - 1) / G::kTileH;
-        const int64_t nblk = (int64_t)a.B * tiles_x * tiles_y;
-        const int groups = (a.CoutP / 32 + MT - 1) / MT;
-        if (nblk > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv2d_fwd: grid too large");
-        auto kern = conv3x3_mfma_kernel<MT, NT, S, D, TWO, 0, FOLD>;
-        static pwc::LdsAttrOnce attr;   // one per instantiation, tracked per device
-        if (const int rc = pwc::ensure_lds_attr(attr, reinterpret_cast<const void *>(kern), G::kSmemBytes, "pwc_conv2d_fwd"))
-            return rc;
-        hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)groups), dim3(kThreads), G::kSmemBytes, a.stream,
-                           a.x, a.wp, a.bias, a.residual, a.y, a.Cin, a.H, a.W, a.Cout, a.CoutP, a.Ho, a.Wo,
-                           tiles_x, tiles_y, a.bsx, a.bsy, a.bsr, a.slope, a.do_leaky, 0, (int64_t)0, a.p16());
-        pwc::note_kernel("conv3x3_mfma_kernel", MT, NT, S, D, TWO, FOLD ? 16 : 0);        // (last field: 16 = folded 8 x 16 tile)
-        return pwc::check_launch("conv3x3_mfma_kernel");
-    }
+    static_assert(G::kValid, "tile does not fit the LDS or the register file");
+    const int tiles_x = (a.Wo + G::kTW - 1) / G::kTW;
+    const int tiles_y = (a.Ho + G::kTileH - 1) / G::kTileH;
+    const int64_t nblk = (int64_t)a.B * tiles_x * tiles_y;
+    const int groups = (a.CoutP / 32 + MT - 1) / MT;
+    if (nblk > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv2d_fwd: grid too large");
+    auto kern = conv3x3_mfma_kernel<MT, NT, S, D, TWO, 0, FOLD>;
+    static pwc::LdsAttrOnce attr;   // one per instantiation, tracked per device
+    if (const int rc = pwc::ensure_lds_attr(attr, reinterpret_cast<const void *>(kern), G::kSmemBytes, "pwc_conv2d_fwd"))
+        return rc;
+    hipLaunchKernelGGL(kern, dim3((unsigned)nblk, (unsigned)groups), dim3(kThreads), G::kSmemBytes, a.stream,
+                       a.x, a.wp, a.bias, a.residual, a.y, a.Cin, a.H, a.W, a.Cout, a.CoutP, a.Ho, a.Wo,
+                       tiles_x, tiles_y, a.bsx, a.bsy, a.bsr, a.slope, a.do_leaky, 0, (int64_t)0, a.p16());
+    pwc::note_kernel("conv3x3_mfma_kernel", MT, NT, S, D, TWO, FOLD ? 16 : 0);        // (last field: 16 = folded 8 x 16 tile)
+    return pwc::check_launch("conv3x3_mfma_kernel");
 }
 
 // split-K launch of the 4x32 x 32-cout tile (CK = 8): raw partials into a.partial
@@ -536,12 +537,48 @@ inline int dispatch16(const ConvArgs &a) {
 // (sweep of 13 variants x 7 level-2 layers at batch 16: profiles/r01_conv_notes.md)
 struct TileChoice { int mt, nt, two; };
 
+// The tiles of each (stride, dilation) unit: a tile is compiled if and only if it is listed here, the model chooses from this list
+// alone, and PWC_CONV_TILE is honoured for its entries only.  The order -- two 0 then 1, mt ascending, nt 1, 2, 4 -- is part of the
+// behaviour: choose_tile keeps the first of equal costs.  Every entry is picked somewhere in the box B 1..32, Cin <= 1001, Cout <= 384,
+// maps up to 256 x 512 (tools/conv_tile_census.hip, profiles/conv_tile_census.txt) and is launched by an audited plan or by a case of
+// launch_audit.TILE_CASES (tests/test_conv_tiles_cpu.py); the one-per-CU forms that fit the register file and the LDS
+// but are never the cheapest there (<1, 2>, <2, 2>; <1, 4>, <2, 4> at small dilations) are not built.
+template <int S, int D> struct Tiles;
+template <> struct Tiles<1, 1> {
+    static constexpr TileChoice list[] = {
+        {1, 1, 0}, {2, 1, 0}, {3, 1, 0}, {3, 2, 0}, {3, 4, 0}, {4, 1, 0}, {4, 2, 0}, {4, 4, 0},
+        {1, 1, 1}, {1, 2, 1}, {1, 4, 1}, {2, 1, 1}, {2, 2, 1}, {2, 4, 1}, {3, 1, 1}, {3, 2, 1}, {4, 1, 1}, {4, 2, 1}};
+};
+template <> struct Tiles<1, 2> {
+    static constexpr TileChoice list[] = {
+        {1, 1, 0}, {2, 1, 0}, {3, 1, 0}, {3, 2, 0}, {3, 4, 0}, {4, 1, 0}, {4, 2, 0}, {4, 4, 0},
+        {1, 1, 1}, {1, 2, 1}, {1, 4, 1}, {2, 1, 1}, {2, 2, 1}, {2, 4, 1}, {3, 1, 1}, {3, 2, 1}, {4, 1, 1}, {4, 2, 1}};
+};
+template <> struct Tiles<1, 4> {
+    static constexpr TileChoice list[] = {
+        {1, 1, 0}, {2, 1, 0}, {2, 4, 0}, {3, 1, 0}, {3, 2, 0}, {3, 4, 0}, {4, 1, 0}, {4, 2, 0}, {4, 4, 0},
+        {1, 1, 1}, {1, 2, 1}, {1, 4, 1}, {2, 1, 1}, {2, 2, 1}, {2, 4, 1}, {3, 1, 1}, {3, 2, 1}, {4, 1, 1}, {4, 2, 1}};
+};
+template <> struct Tiles<1, 8> {
+    static constexpr TileChoice list[] = {
+        {1, 1, 0}, {2, 1, 0}, {3, 1, 0}, {3, 2, 0}, {4, 1, 0}, {4, 2, 0},
+        {1, 1, 1}, {1, 2, 1}, {2, 1, 1}, {2, 2, 1}, {3, 1, 1}, {3, 2, 1}, {4, 1, 1}, {4, 2, 1}};
+};
+template <> struct Tiles<1, 16> {
+    static constexpr TileChoice list[] = {
+        {1, 1, 0}, {2, 1, 0}, {3, 1, 0}, {3, 2, 0},
+        {1, 1, 1}, {1, 2, 1}, {2, 1, 1}, {2, 2, 1}, {3, 1, 1}, {3, 2, 1}};
+};
+template <> struct Tiles<2, 1> {
+    static constexpr TileChoice list[] = {
+        {1, 1, 0}, {2, 1, 0}, {3, 1, 0}, {3, 2, 0}, {4, 1, 0}, {4, 2, 0},
+        {1, 1, 1}, {1, 2, 1}, {2, 1, 1}, {2, 2, 1}, {3, 1, 1}, {3, 2, 1}, {4, 1, 1}, {4, 2, 1}};
+};
+
 template <int S, int D>
-constexpr bool variant_valid(int mt, int nt, int two) {
-#define PWC_V(MT_, NT_) if (mt == MT_ && nt == NT_) return two ? Geom<MT_, NT_, S, D, 1>::kValid : Geom<MT_, NT_, S, D, 0>::kValid;
-    PWC_V(1, 1) PWC_V(2, 1) PWC_V(3, 1) PWC_V(4, 1) PWC_V(1, 2) PWC_V(2, 2) PWC_V(3, 2) PWC_V(4, 2)
-    PWC_V(1, 4) PWC_V(2, 4) PWC_V(3, 4) PWC_V(4, 4)
-#undef PWC_V
+inline bool in_table(TileChoice t) {
+    for (const TileChoice &e : Tiles<S, D>::list)
+        if (e.mt == t.mt && e.nt == t.nt && e.two == t.two) return true;
     return false;
 }
 
@@ -551,76 +588,72 @@ inline bool tune_l2() {        // PWC_CONV_NO_TUNE_L2=1: the cost model without 
 }
 
 template <int S, int D>
-inline TileChoice choose_tile(int B, int Cin, int Ho, int Wo, int CoutP, int max_nt, int max_mt, int force_two) {
+inline TileChoice choose_tile(int B, int Cin, int Ho, int Wo, int CoutP, int force_two) {
     const int tiles32 = CoutP / 32;
     const int tiles_x = (Wo + kTileW - 1) / kTileW;
     const double chunks8 = (Cin + 7) / 8;
     TileChoice best{1, 1, 0};
     double best_cost = 1e300;
-    for (int two = 0; two <= 1; ++two) {
-        if (force_two >= 0 && two != force_two) continue;
-        for (int mt = 1; mt <= max_mt; ++mt) {
-            if (mt > tiles32) break;
-            const int groups = (tiles32 + mt - 1) / mt;
-            for (int nt = 1; nt <= max_nt; nt *= 2) {
-                if (!variant_valid<S, D>(mt, nt, two)) continue;
-                const int tiles_y = (Ho + 4 * nt - 1) / (4 * nt);
-                const double blocks = (double)B * tiles_x * tiles_y * groups;
-                double cost;
-                if (!two) {
-                    // equal-length workgroups, one per CU: discrete rounds
-                    const double rounds = (double)(int64_t)((blocks + 255.0) / 256.0);
-                    cost = rounds * (chunks8 * (mt * nt + 0.45) + 20.0);
-                } else if (blocks <= 256.0) {
-                    cost = chunks8 * (mt * nt + 0.75) + 20.0;      // alone on its CU, twice the barriers (CK=4)
-                } else if (blocks <= 512.0) {
-                    cost = chunks8 * 2.0 * mt * nt + 5.0;           // the busiest CU holds two
-                } else {
-                    // workgroups retire and start independently: work / throughput + a quarter-round tail
-                    cost = (blocks / 512.0 + 0.25) * (chunks8 * 2.0 * mt * nt + 5.0);
-                    if (mt == 3) cost *= 1.12;                      // measured: the 96-wide variant under-performs here
-                }
-                cost *= 1.0 + 0.02 * (groups - 1);               // mild penalty: input re-read per cout group
-                if (S == 1 && two && blocks > 512.0 && tune_l2()) {
-                    // measured residuals of the model on the level-2 layers at batch 16 (19-variant sweep after the
-                    // XCD-aware tile order, profiles/r01_conv_notes.md): 8-row tiles halve the halo share of the
-                    // staging for 32-cout layers and for dilation 4; with dilation 16 the 4-row tile wins
-                    if (D == 1 && tiles32 == 1 && nt == 1) cost *= 1.045;
-                    if (D == 4 && nt == 1) cost *= 1.04;
-                    if (D == 16 && nt > 1) cost *= 1.05;
-                }
-                if (cost < best_cost) { best_cost = cost; best = {mt, nt, two}; }
-            }
+    for (const TileChoice &e : Tiles<S, D>::list) {
+        const int mt = e.mt, nt = e.nt, two = e.two;
+        if ((force_two >= 0 && two != force_two) || mt > tiles32) continue;
+        const int groups = (tiles32 + mt - 1) / mt;
+        const int tiles_y = (Ho + 4 * nt - 1) / (4 * nt);
+        const double blocks = (double)B * tiles_x * tiles_y * groups;
+        double cost;
+        if (!two) {
+            // equal-length workgroups, one per CU: discrete rounds
+            const double rounds = (double)(int64_t)((blocks + 255.0) / 256.0);
+            cost = rounds * (chunks8 * (mt * nt + 0.45) + 20.0);
+        } else if (blocks <= 256.0) {
+            cost = chunks8 * (mt * nt + 0.75) + 20.0;      // alone on its CU, twice the barriers (CK=4)
+        } else if (blocks <= 512.0) {
+            cost = chunks8 * 2.0 * mt * nt + 5.0;           // the busiest CU holds two
+        } else {
+            // workgroups retire and start independently: work / throughput + a quarter-round tail
+            cost = (blocks / 512.0 + 0.25) * (chunks8 * 2.0 * mt * nt + 5.0);
+            if (mt == 3) cost *= 1.12;                      // measured: the 96-wide variant under-performs here
         }
+        cost *= 1.0 + 0.02 * (groups - 1);               // mild penalty: input re-read per cout group
+        if (S == 1 && two && blocks > 512.0 && tune_l2()) {
+            // measured residuals of the model on the level-2 layers at batch 16 (19-variant sweep after the
+            // XCD-aware tile order, profiles/r01_conv_notes.md): 8-row tiles halve the halo share of the
+            // staging for 32-cout layers and for dilation 4; with dilation 16 the 4-row tile wins
+            if (D == 1 && tiles32 == 1 && nt == 1) cost *= 1.045;
+            if (D == 4 && nt == 1) cost *= 1.04;
+            if (D == 16 && nt > 1) cost *= 1.05;
+        }
+        if (cost < best_cost) { best_cost = cost; best = e; }
     }
     return best;
 }
 
+// launch the entry of the unit's table that equals t: a fold over the table, one launch<> instantiation per entry
+template <int S, int D, size_t... I>
+int launch_tile(const ConvArgs &a, TileChoice t, std::index_sequence<I...>) {
+    constexpr auto &L = Tiles<S, D>::list;
+    int rc = PWC_EINVAL;
+    const bool found = ((L[I].mt == t.mt && L[I].nt == t.nt && L[I].two == t.two &&
+                         (rc = launch<L[I].mt, L[I].nt, S, D, L[I].two>(a), true)) || ...);
+    if (!found) PWC_FAIL(PWC_EINVAL, "pwc_conv2d_fwd: internal tile choice %dx%d", t.mt, t.nt);
+    return rc;
+}
+
 // one of these per translation unit
-template <int S, int D, int MAXNT, int MAXMT>
+template <int S, int D>
 int dispatch(const ConvArgs &a) {
     static const int force_two = [] { const char *e = getenv("PWC_CONV_TWO"); return (e && *e) ? atoi(e) : -1; }();
-    TileChoice t = choose_tile<S, D>(a.B, a.Cin, a.Ho, a.Wo, a.CoutP, MAXNT, MAXMT, force_two);
-    if (force_two >= 0 && !variant_valid<S, D>(t.mt, t.nt, t.two))
-        t = choose_tile<S, D>(a.B, a.Cin, a.Ho, a.Wo, a.CoutP, MAXNT, MAXMT, -1);
+    TileChoice t = choose_tile<S, D>(a.B, a.Cin, a.Ho, a.Wo, a.CoutP, force_two);
     // tuning knob: PWC_CONV_TILE="mt,nt,two" overrides the model when that variant exists for this layer
     static const TileChoice forced = [] {
         TileChoice f{0, 0, 0};
         const char *e = getenv("PWC_CONV_TILE");
         if (e) sscanf(e, "%d,%d,%d", &f.mt, &f.nt, &f.two);
+        f.two = f.two ? 1 : 0;
         return f;
     }();
-    if (forced.mt > 0 && forced.mt <= MAXMT && forced.nt <= MAXNT && forced.mt * 32 <= a.CoutP + 31 &&
-        variant_valid<S, D>(forced.mt, forced.nt, forced.two))
-        t = forced;
-#define PWC_TILE(MT_, NT_)                                                                       \
-    if (t.mt == MT_ && t.nt == NT_) return t.two ? launch<MT_, NT_, S, D, 1>(a) : launch<MT_, NT_, S, D, 0>(a);
-    PWC_TILE(1, 1) PWC_TILE(2, 1) PWC_TILE(3, 1)
-    PWC_TILE(1, 2) PWC_TILE(2, 2) PWC_TILE(3, 2)
-    if constexpr (MAXMT >= 4) { PWC_TILE(4, 1) PWC_TILE(4, 2) }
-    if constexpr (MAXNT >= 4) { PWC_TILE(1, 4) PWC_TILE(2, 4) PWC_TILE(3, 4) PWC_TILE(4, 4) }
-#undef PWC_TILE
-    PWC_FAIL(PWC_EINVAL, "pwc_conv2d_fwd: internal tile choice %dx%d", t.mt, t.nt);
+    if (forced.mt * 32 <= a.CoutP + 31 && in_table<S, D>(forced)) t = forced;
+    return launch_tile<S, D>(a, t, std::make_index_sequence<std::size(Tiles<S, D>::list)>{});
 }
 
 }  // namespace (anonymous)

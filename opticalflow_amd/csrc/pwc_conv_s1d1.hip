@@ -7,6 +7,6 @@ int run_s1d1(const ConvArgs &a) {
     static const bool use16 = [] { const char *e = getenv("PWC_CONV16"); return !(e && *e == '0'); }();
     if (a.Cout <= 16 && use16) return dispatch16(a);
     if (fold) return launch<1, 1, 1, 1, 1, 1>(a);   // two workgroups per CU (4-channel chunks), as the tile model picks for these layers
-    return dispatch<1, 1, 4, 4>(a);
+    return dispatch<1, 1>(a);
 }
 }  // namespace pwc_conv

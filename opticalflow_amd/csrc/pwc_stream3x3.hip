@@ -440,7 +440,7 @@ int launch_cfg(const float *x, int B, int Cin, int H, int W, int64_t bsx,
     return pwc::check_launch("stream3x3_kernel");
 }
 
-// PWC_STREAM_CFG=81|42|44 pins the tile shape (experiments); default: <4,4> when 8-row tiles would leave CUs idle.
+// PWC_STREAM_CFG=81|44 pins the tile shape (experiments); default: <4,4> when 8-row tiles would leave CUs idle.
 inline int stream_cfg_override() {
     static const int v = [] { const char *e = getenv("PWC_STREAM_CFG"); return e ? atoi(e) : 0; }();
     return v;
@@ -466,11 +466,9 @@ int launch(const float *x, int B, int Cin, int H, int W, int64_t bsx,
         return pwc::check_launch("stream3x3_slice_reduce_kernel");
     }
     int cfg = stream_cfg_override();
-    if (cfg != 81 && cfg != 42 && cfg != 44 && cfg != 41) cfg = nblk8 < 256 ? 44 : 81;
+    if (cfg != 81 && cfg != 44) cfg = nblk8 < 256 ? 44 : 81;
 #define PWC_STREAM_GO(TH, KS) return launch_cfg<MODE, TH, KS>(x, B, Cin, H, W, bsx, hw, hbias, residual, hy, bshy, bsr, slope, do_leaky, uw, ubias, uy, bsuy, st)
     if (cfg == 44) PWC_STREAM_GO(4, 4);
-    if (cfg == 42) PWC_STREAM_GO(4, 2);
-    if (cfg == 41) PWC_STREAM_GO(4, 1);
     PWC_STREAM_GO(8, 1);
 #undef PWC_STREAM_GO
 }

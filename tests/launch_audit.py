@@ -134,6 +134,88 @@ KERNELS_REQUIRED = (
     "stream3x3_kernel<3, 4, 4, 1, 0, 0>",
 )
 
+# ---- tile instantiations of the direct kernel that no fp32 plan launches (test_gpu_parity.test_conv3x3_tile_instantiations_vs_fp64) ----
+# Every entry of pwc_conv_mfma.h's tile tables that KERNELS_REQUIRED does not hold (tests/test_conv_tiles_cpu.py asserts that the two
+# together are exactly the tables), each at a shape for which the cost model (choose_tile) picks it, the cheapest that
+# tools/conv_tile_census.hip finds (profiles/conv_tile_census.txt): (B, Cin, Cout, H, W, stride, dilation, kernel).
+# Cin is ragged against the 4- / 8-channel chunks, W against the 32-column tile, H against the 4 NT-row tile wherever the model allows.
+# The two-per-CU variants (fifth argument 1) need more than 256 workgroups, the one-per-CU 96-cout ones a long K loop: hence B and Cin
+TILE_CASES = [
+    (1, 5, 196, 4, 20, 1, 1, "conv3x3_mfma_kernel<2, 1, 1, 1, 0, 0>"),
+    (4, 197, 384, 30, 36, 1, 1, "conv3x3_mfma_kernel<3, 1, 1, 1, 0, 0>"),
+    (4, 197, 288, 250, 36, 1, 1, "conv3x3_mfma_kernel<3, 2, 1, 1, 0, 0>"),
+    (8, 101, 96, 250, 100, 1, 1, "conv3x3_mfma_kernel<3, 4, 1, 1, 0, 0>"),
+    (32, 861, 356, 2, 228, 1, 1, "conv3x3_mfma_kernel<4, 1, 1, 1, 0, 0>"),
+    (32, 541, 324, 5, 228, 1, 1, "conv3x3_mfma_kernel<4, 2, 1, 1, 0, 0>"),
+    (32, 141, 100, 125, 36, 1, 1, "conv3x3_mfma_kernel<4, 4, 1, 1, 0, 0>"),
+    (12, 13, 32, 100, 36, 1, 1, "conv3x3_mfma_kernel<1, 2, 1, 1, 1, 0>"),
+    (32, 13, 160, 9, 72, 1, 1, "conv3x3_mfma_kernel<1, 4, 1, 1, 1, 0>"),
+    (12, 13, 256, 9, 36, 1, 1, "conv3x3_mfma_kernel<2, 1, 1, 1, 1, 0>"),
+    (7, 13, 48, 200, 36, 1, 1, "conv3x3_mfma_kernel<2, 2, 1, 1, 1, 0>"),
+    (32, 13, 48, 100, 36, 1, 1, "conv3x3_mfma_kernel<2, 4, 1, 1, 1, 0>"),
+    (20, 13, 160, 36, 36, 1, 1, "conv3x3_mfma_kernel<3, 2, 1, 1, 1, 0>"),
+    (32, 13, 196, 9, 36, 1, 1, "conv3x3_mfma_kernel<4, 1, 1, 1, 1, 0>"),
+    (32, 13, 100, 50, 36, 1, 1, "conv3x3_mfma_kernel<4, 2, 1, 1, 1, 0>"),
+    (1, 5, 196, 4, 20, 1, 2, "conv3x3_mfma_kernel<2, 1, 1, 2, 0, 0>"),
+    (4, 197, 384, 30, 36, 1, 2, "conv3x3_mfma_kernel<3, 1, 1, 2, 0, 0>"),
+    (4, 197, 288, 250, 36, 1, 2, "conv3x3_mfma_kernel<3, 2, 1, 2, 0, 0>"),
+    (8, 101, 96, 250, 100, 1, 2, "conv3x3_mfma_kernel<3, 4, 1, 2, 0, 0>"),
+    (32, 861, 356, 3, 228, 1, 2, "conv3x3_mfma_kernel<4, 1, 1, 2, 0, 0>"),
+    (32, 541, 324, 5, 228, 1, 2, "conv3x3_mfma_kernel<4, 2, 1, 2, 0, 0>"),
+    (32, 141, 100, 125, 36, 1, 2, "conv3x3_mfma_kernel<4, 4, 1, 2, 0, 0>"),
+    (5, 13, 32, 250, 36, 1, 2, "conv3x3_mfma_kernel<1, 2, 1, 2, 1, 0>"),
+    (32, 13, 160, 9, 72, 1, 2, "conv3x3_mfma_kernel<1, 4, 1, 2, 1, 0>"),
+    (7, 13, 48, 200, 36, 1, 2, "conv3x3_mfma_kernel<2, 2, 1, 2, 1, 0>"),
+    (32, 13, 48, 100, 36, 1, 2, "conv3x3_mfma_kernel<2, 4, 1, 2, 1, 0>"),
+    (32, 13, 160, 9, 36, 1, 2, "conv3x3_mfma_kernel<3, 1, 1, 2, 1, 0>"),
+    (20, 13, 160, 36, 36, 1, 2, "conv3x3_mfma_kernel<3, 2, 1, 2, 1, 0>"),
+    (32, 13, 196, 9, 36, 1, 2, "conv3x3_mfma_kernel<4, 1, 1, 2, 1, 0>"),
+    (32, 13, 100, 50, 36, 1, 2, "conv3x3_mfma_kernel<4, 2, 1, 2, 1, 0>"),
+    (1, 5, 196, 4, 20, 1, 4, "conv3x3_mfma_kernel<2, 1, 1, 4, 0, 0>"),
+    (17, 629, 292, 141, 20, 1, 4, "conv3x3_mfma_kernel<2, 4, 1, 4, 0, 0>"),
+    (1, 197, 384, 120, 36, 1, 4, "conv3x3_mfma_kernel<3, 1, 1, 4, 0, 0>"),
+    (4, 197, 288, 250, 36, 1, 4, "conv3x3_mfma_kernel<3, 2, 1, 4, 0, 0>"),
+    (8, 101, 288, 60, 136, 1, 4, "conv3x3_mfma_kernel<3, 4, 1, 4, 0, 0>"),
+    (32, 485, 228, 21, 36, 1, 4, "conv3x3_mfma_kernel<4, 1, 1, 4, 0, 0>"),
+    (32, 205, 324, 5, 228, 1, 4, "conv3x3_mfma_kernel<4, 2, 1, 4, 0, 0>"),
+    (8, 101, 256, 250, 36, 1, 4, "conv3x3_mfma_kernel<4, 4, 1, 4, 0, 0>"),
+    (32, 13, 160, 9, 72, 1, 4, "conv3x3_mfma_kernel<1, 4, 1, 4, 1, 0>"),
+    (7, 13, 48, 200, 36, 1, 4, "conv3x3_mfma_kernel<2, 2, 1, 4, 1, 0>"),
+    (32, 13, 48, 100, 36, 1, 4, "conv3x3_mfma_kernel<2, 4, 1, 4, 1, 0>"),
+    (32, 13, 160, 9, 36, 1, 4, "conv3x3_mfma_kernel<3, 1, 1, 4, 1, 0>"),
+    (32, 13, 160, 18, 36, 1, 4, "conv3x3_mfma_kernel<3, 2, 1, 4, 1, 0>"),
+    (32, 13, 196, 9, 36, 1, 4, "conv3x3_mfma_kernel<4, 1, 1, 4, 1, 0>"),
+    (5, 13, 196, 150, 36, 1, 4, "conv3x3_mfma_kernel<4, 2, 1, 4, 1, 0>"),
+    (1, 5, 196, 4, 20, 1, 8, "conv3x3_mfma_kernel<2, 1, 1, 8, 0, 0>"),
+    (4, 197, 384, 30, 36, 1, 8, "conv3x3_mfma_kernel<3, 1, 1, 8, 0, 0>"),
+    (4, 197, 288, 250, 36, 1, 8, "conv3x3_mfma_kernel<3, 2, 1, 8, 0, 0>"),
+    (17, 981, 356, 57, 20, 1, 8, "conv3x3_mfma_kernel<4, 1, 1, 8, 0, 0>"),
+    (32, 541, 324, 29, 36, 1, 8, "conv3x3_mfma_kernel<4, 2, 1, 8, 0, 0>"),
+    (12, 13, 256, 9, 36, 1, 8, "conv3x3_mfma_kernel<2, 1, 1, 8, 1, 0>"),
+    (7, 13, 48, 200, 36, 1, 8, "conv3x3_mfma_kernel<2, 2, 1, 8, 1, 0>"),
+    (32, 13, 160, 9, 36, 1, 8, "conv3x3_mfma_kernel<3, 1, 1, 8, 1, 0>"),
+    (20, 13, 160, 36, 36, 1, 8, "conv3x3_mfma_kernel<3, 2, 1, 8, 1, 0>"),
+    (32, 13, 196, 9, 36, 1, 8, "conv3x3_mfma_kernel<4, 1, 1, 8, 1, 0>"),
+    (32, 13, 100, 50, 36, 1, 8, "conv3x3_mfma_kernel<4, 2, 1, 8, 1, 0>"),
+    (1, 5, 196, 4, 20, 1, 16, "conv3x3_mfma_kernel<2, 1, 1, 16, 0, 0>"),
+    (4, 197, 384, 30, 36, 1, 16, "conv3x3_mfma_kernel<3, 1, 1, 16, 0, 0>"),
+    (4, 197, 288, 250, 36, 1, 16, "conv3x3_mfma_kernel<3, 2, 1, 16, 0, 0>"),
+    (5, 13, 32, 250, 36, 1, 16, "conv3x3_mfma_kernel<1, 2, 1, 16, 1, 0>"),
+    (12, 13, 256, 9, 36, 1, 16, "conv3x3_mfma_kernel<2, 1, 1, 16, 1, 0>"),
+    (32, 13, 196, 9, 36, 1, 16, "conv3x3_mfma_kernel<2, 2, 1, 16, 1, 0>"),
+    (32, 13, 160, 9, 36, 1, 16, "conv3x3_mfma_kernel<3, 1, 1, 16, 1, 0>"),
+    (7, 13, 196, 75, 36, 1, 16, "conv3x3_mfma_kernel<3, 2, 1, 16, 1, 0>"),
+    (1, 5, 196, 4, 20, 2, 1, "conv3x3_mfma_kernel<2, 1, 2, 1, 0, 0>"),
+    (8, 197, 384, 10, 200, 2, 1, "conv3x3_mfma_kernel<3, 1, 2, 1, 0, 0>"),
+    (8, 197, 288, 250, 72, 2, 1, "conv3x3_mfma_kernel<3, 2, 2, 1, 0, 0>"),
+    (32, 861, 356, 3, 456, 2, 1, "conv3x3_mfma_kernel<4, 1, 2, 1, 0, 0>"),
+    (32, 541, 324, 57, 72, 2, 1, "conv3x3_mfma_kernel<4, 2, 2, 1, 0, 0>"),
+    (32, 13, 196, 9, 136, 2, 1, "conv3x3_mfma_kernel<4, 1, 2, 1, 1, 0>"),
+    (20, 13, 196, 75, 72, 2, 1, "conv3x3_mfma_kernel<4, 2, 2, 1, 1, 0>"),
+    (4, 16, 16, 224, 512, 1, 1, "conv3x3_mfma16_kernel<2, 4, 1, 1, 0, 0>"),       # the 16-cout kernel's 8-row ...
+    (10, 16, 16, 224, 500, 1, 1, "conv3x3_mfma16_kernel<4, 4, 1, 1, 0, 0>"),      # ... and 16-row tiles
+]
+
 OPS = ("densify", "conv3x3", "conv3x3_wino", "conv3x3_wino4", "pyr1_wino", "pyr1_wino_pair", "warp_correlation", "warp", "correlation",
        "head_upfeat", "upsample_entry", "deconv4x4s2", "lattice_unsplit")
 

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """predict_flowL + upfeatL (pwc_head_upfeat_fwd) alone at the level-4 / level-3 geometries of batch 16, HIP events, three operand sets in
-rotation; PWC_STREAM_CFG=81|42|44|41 pins the tile shape (one process each).  python tools/experiments/head_upfeat_cfg.py"""
+rotation; PWC_STREAM_CFG=81|44 pins the tile shape (one process each).  python tools/experiments/head_upfeat_cfg.py"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from opticalflow_amd import ops, _lib

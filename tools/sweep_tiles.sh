@@ -4,7 +4,7 @@
 cd "$(dirname "$0")/.."
 run() {  # geom, cases...
   local geom=$1; shift
-  for tile in auto 1,1,0 1,1,1 2,1,0 2,1,1 3,1,1 4,1,1 1,2,0 1,2,1 2,2,0 2,2,1 4,2,1 1,4,0 1,4,1 2,4,0 2,4,1 4,4,0; do
+  for tile in auto 1,1,0 1,1,1 2,1,0 2,1,1 3,1,1 4,1,1 1,2,1 2,2,1 4,2,1 1,4,1 2,4,1 4,4,0; do
     if [ "$tile" = "auto" ]; then unset PWC_CONV_TILE; else export PWC_CONV_TILE=$tile; fi
     echo "== geom $geom tile $tile"
     PWC_BENCH_GEOM=$geom python tools/bench_conv.py "$@" 2>&1 | grep -v amdgpu.ids
