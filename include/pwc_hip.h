@@ -38,6 +38,8 @@
  *                       crop, horizontal flip) from the raw uint8 frames and the ground truth, only the cropped window computed
  *   pwc_kitti_augment_full   KittiAugmentationPipeline data_processing.py:136-279 (train2.py's collate_fn: crop, flip, rotation,
  *                       translation, brightness / contrast, Gaussian blur) from the same raw inputs
+ *   pwc_optim_*         the optimizer step of the four scripts: optim.Adam train.py:129 (under GradScaler.step), train_pseudo.py:423,
+ *                       train_fundamental.py:599 (L2 weight decay); clip_grad_norm_ + optim.AdamW train2.py:193, :370
  *   pwc_conv2d_fwd      conv()/predict_flow()     models/PWCNet.py:26-33 (nn.Conv2d 3x3 + LeakyReLU(0.1))
  *   pwc_deconv4x4s2_fwd deconv()                  models/PWCNet.py:35-36 (nn.ConvTranspose2d k4 s2 p1)
  *
@@ -812,6 +814,46 @@ int pwc_head_upfeat_ws_fwd(const void *x, const void *head_wp, const void *head_
                            int B, int Cin, int H, int W, int dtype,
                            int64_t x_bstride, int64_t flow_bstride, int64_t up_bstride,
                            void *workspace, int64_t workspace_bytes, void *stream);
+
+/* Adam / AdamW step with global-norm gradient clipping over all tensors of an optimizer (opticalflow_amd/optim.py): what the
+ * reference's scripts do with clip_grad_norm_ + optimizer.step() (train2.py), Adam + L2 weight decay (train_pseudo.py,
+ * train_fundamental.py) and GradScaler.step(optimizer) (train.py), as three launches -- square sum, finish, update -- without a host
+ * synchronisation.  fp32 parameters, gradients and moments only.
+ *
+ * Every tensor is cut into chunks of pwc_optim_chunk_elems() elements, one workgroup each.  The caller keeps three device tables:
+ *   tensors  [ntensors] {float *p, *m, *v; int64_t numel}    parameter, exp_avg, exp_avg_sq (dense); changes with the parameter set
+ *   grads    [ntensors] const float *                        this step's gradients; NULL leaves the tensor out of the step
+ *   chunks   [nchunks]  {int32 tensor, int32 chunk}          chunk `chunk` of tensor `tensor` = its elements [chunk * K, (chunk + 1) * K)
+ * and a workspace of pwc_optim_workspace_bytes(nchunks, ngroups) bytes (8-byte aligned): one fp64 partial per chunk, then one record
+ * of constants per parameter group.  The tables are trusted: an entry that does not describe live memory is a wild access.
+ *
+ * pwc_optim_grad_sqsum   partial[i] = sum of g^2 over chunk i, each product and the sum in fp64, fixed order, no atomics.
+ * pwc_optim_finish       for one group: the partials added in index order, total_norm = (float)sqrt(sum) * (1 / grad_scale),
+ *                        coef = min(1, max_norm / (total_norm + 1e-6f)) in fp32 (torch's clip_grad_norm_); clip = 0: partials not
+ *                        read, coef = 1, norm_out not written.  found_inf / grad_scale: optional fp32 device scalars (GradScaler's
+ *                        protocol for optimizers with _step_supports_amp_scaling).  found_inf != 0 marks the step skipped;
+ *                        otherwise step_record[group] = {double step, beta1^step, beta2^step} advances by one step (running
+ *                        products).  The group's constants {step_size = lr / (1 - beta1^step), bc2_sqrt = sqrt(1 - beta2^step),
+ *                        each formed in fp64 and rounded once, coef, 1 / grad_scale, skipped} go to the workspace and total_norm to
+ *                        norm_out.  A new record is {0, 1, 1}.
+ * pwc_optim_adam_update  chunks [chunk_begin, chunk_begin + chunk_count) (one group's) with the group's constants; per element,
+ *                        in fp32 and in this order (nothing is written when the step is skipped; g itself is never modified):
+ *                          g = (g * inv_scale) * coef;  weight_decay != 0: g = g + wd * p (L2) or p = p * (1 - lr * wd) (decoupled)
+ *                          m = m + (1 - b1) * (g - m);  v = v * b2 + (1 - b2) * (g * g)
+ *                          p = p + (-step_size) * (m / (sqrt(v) / bc2_sqrt + eps))
+ *                        with correctly rounded division and square root, and 1 - b1, 1 - b2, 1 - lr * wd formed in fp64 and rounded
+ *                        once.  16-byte accesses where g, p, m and v of a tensor are all 16-byte aligned, 4-byte ones otherwise. */
+int pwc_optim_chunk_elems(void);
+int64_t pwc_optim_workspace_bytes(int64_t nchunks, int ngroups);
+int pwc_optim_grad_sqsum(const void *grads, const void *tensors, const void *chunks, int64_t nchunks, int ngroups,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+int pwc_optim_finish(void *workspace, int64_t workspace_bytes, int64_t nchunks, int ngroups, int group, int clip,
+                     double max_norm, const void *found_inf, const void *grad_scale, double lr, double beta1,
+                     double beta2, void *step_record, void *norm_out, void *stream);
+int pwc_optim_adam_update(const void *grads, const void *tensors, const void *chunks, int64_t nchunks, int64_t chunk_begin,
+                          int64_t chunk_count, int ngroups, int group, const void *workspace, int64_t workspace_bytes,
+                          double lr, double beta1, double beta2, double eps, double weight_decay, int decoupled,
+                          void *stream);
 
 /* Profiling calibration, not on the product path: streams `nbytes` (a multiple of 64*width) of src through LDS with the
  * kernels' own LDS-DMA instruction (width 4: buffer_load_dword ... lds, width 16: buffer_load_dwordx4 ... lds) so that rocprofv3's

@@ -11,5 +11,7 @@ from . import augment  # noqa: F401
 from .augment import DeviceAugmenter, augment_batch  # noqa: F401
 from . import augment_full  # noqa: F401
 from .augment_full import DeviceFullAugmenter, augment_full_batch  # noqa: F401
+from . import optim  # noqa: F401
+from .optim import FusedAdam, FusedAdamW  # noqa: F401
 
 __version__ = "0.1.0"

@@ -137,3 +137,23 @@ def _mask_arg(mask: Optional[torch.Tensor], B: int, H: int, W: int, device, rule
     else:
         m, u8 = ((mask > 0.5) if rule == "threshold" else (mask != 0)).contiguous().view(torch.uint8), 1
     return m, u8, H * W
+
+
+def _table_arg(t: torch.Tensor, dtype, min_numel: int, device, name: str) -> int:
+    """Device pointer of a contiguous table of at least min_numel elements of this dtype on this device (the kernels trust its
+    contents; its placement is checked here)."""
+    _require_device(t, name)
+    if t.dtype != dtype or t.device != device or not t.is_contiguous() or t.numel() < min_numel:
+        raise ValueError("%s must be a contiguous %s table of at least %d elements on %s, got %s[%d] on %s"
+                         % (name, dtype, min_numel, device, t.dtype, t.numel(), t.device))
+    return t.data_ptr()
+
+
+def _scalar_arg(t: Optional[torch.Tensor], device, name: str) -> Optional[int]:
+    """Device pointer of an optional one-element float32 scalar on this device (None = NULL)."""
+    if t is None:
+        return None
+    _require_device(t, name)
+    if t.dtype != torch.float32 or t.numel() != 1 or t.device != device:
+        raise ValueError("%s must be one float32 element on %s, got %s[%d] on %s" % (name, device, t.dtype, t.numel(), t.device))
+    return t.data_ptr()

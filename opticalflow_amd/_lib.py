@@ -111,6 +111,13 @@ SIGNATURES = {
                                 c_void_p, c_int64, c_float] + [c_void_p] * 4),
     "pwc_kitti_augment": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 6),
     "pwc_kitti_augment_full": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 6),
+    "pwc_optim_chunk_elems": (c_int, []),
+    "pwc_optim_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "pwc_optim_grad_sqsum": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_void_p, c_int64, c_void_p]),
+    "pwc_optim_finish": (c_int, [c_void_p, c_int64, c_int64, c_int, c_int, c_int, c_double, c_void_p, c_void_p] + [c_double] * 3
+                         + [c_void_p] * 3),
+    "pwc_optim_adam_update": (c_int, [c_void_p] * 3 + [c_int64] * 3 + [c_int, c_int, c_void_p, c_int64] + [c_double] * 5
+                              + [c_int, c_void_p]),
     "pwc_lattice_unsplit_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
     "pwc_conv2d_f16_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                    c_uint, c_float, c_int64, c_int64, c_void_p]),

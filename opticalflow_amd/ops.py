@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._args import (_bias_arg, _dtype_code, _f32_dense, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr, _query_bytes,
-                    _require_device, _scratch, _stream, _workspace_args, densify)
+                    _require_device, _scalar_arg, _scratch, _stream, _table_arg, _workspace_args, densify)
 from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F32, PwcHipError, check)
 
 def corr_output_shape(C: int, H: int, W: int, pad_size: int, kernel_size: int, max_displacement: int,
@@ -1390,3 +1390,63 @@ class EpipolarSampsonFunction(torch.autograd.Function):
         F, ok, m = ctx.consts
         gf = epipolar_loss_backward(flow, F, ok, m, grad_out, *ctx.cfg)
         return gf, None, None, None, None, None, None
+
+
+# ---------------------------------------------------------------- fused Adam / AdamW step with gradient clipping (optim.py)
+def optim_chunk_elems() -> int:
+    """Elements of one chunk (one workgroup) of the optimizer kernels; the host's chunk table is cut with it."""
+    return int(_lib.load().pwc_optim_chunk_elems())
+
+
+def optim_workspace_bytes(nchunks: int, ngroups: int) -> int:
+    return _query_bytes(_lib.load().pwc_optim_workspace_bytes(int(nchunks), int(ngroups)), "optimizer workspace")
+
+
+def _optim_tables(grads: torch.Tensor, tensors: torch.Tensor, chunks: torch.Tensor, nchunks: int):
+    dev = grads.device
+    ntensors = grads.numel()
+    return (_table_arg(grads, torch.int64, 1, dev, "grads"), _table_arg(tensors, torch.int64, 4 * ntensors, dev, "tensors"),
+            _table_arg(chunks, torch.int32, 2 * nchunks, dev, "chunks"))
+
+
+def optim_grad_sqsum(grads: torch.Tensor, tensors: torch.Tensor, chunks: torch.Tensor, nchunks: int, ngroups: int,
+                     workspace: torch.Tensor) -> None:
+    """pwc_optim_grad_sqsum: one float64 partial of the sum of g^2 per chunk into the workspace.  grads int64 [ntensors] (device
+    addresses, 0 = no gradient), tensors int64 [ntensors, 4] = (p, m, v, numel), chunks int32 [nchunks, 2] = (tensor, chunk)."""
+    pg, pt, pc = _optim_tables(grads, tensors, chunks, nchunks)
+    pw, nb = _workspace_args(workspace, grads)
+    with torch.cuda.device(grads.device):
+        rc = _lib.load().pwc_optim_grad_sqsum(pg, pt, pc, nchunks, ngroups, pw, nb, _stream(grads))
+    check(rc, "pwc_optim_grad_sqsum")
+
+
+def optim_finish(workspace: torch.Tensor, nchunks: int, ngroups: int, group: int, max_norm: Optional[float],
+                 found_inf: Optional[torch.Tensor], grad_scale: Optional[torch.Tensor], lr: float, beta1: float, beta2: float,
+                 step_record: torch.Tensor, norm_out: Optional[torch.Tensor]) -> None:
+    """pwc_optim_finish for one parameter group: total norm and clip coefficient from the partials (max_norm None: no clipping,
+    coefficient 1), GradScaler's found_inf / grad_scale, step_record float64 [ngroups, 3] = (step, beta1^step, beta2^step) advanced
+    unless the step is skipped, the constants of the update written to the workspace."""
+    dev = workspace.device
+    pw, nb = _workspace_args(workspace, workspace)
+    clip = max_norm is not None
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_optim_finish(pw, nb, nchunks, ngroups, group, int(clip), float(max_norm) if clip else 0.0,
+                                          _scalar_arg(found_inf, dev, "found_inf"), _scalar_arg(grad_scale, dev, "grad_scale"),
+                                          float(lr), float(beta1), float(beta2),
+                                          _table_arg(step_record, torch.float64, 3 * ngroups, dev, "step_record"),
+                                          _scalar_arg(norm_out, dev, "norm_out"), _stream(workspace))
+    check(rc, "pwc_optim_finish")
+
+
+def optim_adam_update(grads: torch.Tensor, tensors: torch.Tensor, chunks: torch.Tensor, nchunks: int, chunk_begin: int,
+                      chunk_count: int, ngroups: int, group: int, workspace: torch.Tensor, lr: float, beta1: float, beta2: float,
+                      eps: float, weight_decay: float, decoupled: bool) -> None:
+    """pwc_optim_adam_update: p, m, v of the chunks [chunk_begin, chunk_begin + chunk_count) updated in place with the constants
+    pwc_optim_finish left for this group (include/pwc_hip.h has the arithmetic); the gradients are not modified."""
+    pg, pt, pc = _optim_tables(grads, tensors, chunks, nchunks)
+    pw, nb = _workspace_args(workspace, grads)
+    with torch.cuda.device(grads.device):
+        rc = _lib.load().pwc_optim_adam_update(pg, pt, pc, nchunks, chunk_begin, chunk_count, ngroups, group, pw, nb, float(lr),
+                                               float(beta1), float(beta2), float(eps), float(weight_decay), int(bool(decoupled)),
+                                               _stream(grads))
+    check(rc, "pwc_optim_adam_update")
