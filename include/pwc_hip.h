@@ -556,6 +556,37 @@ int pwc_flow_quiver(const void *flow, int n, int Hq, int Wq, int crop_h, int cro
                     const void *dominant /* may be NULL */, int64_t dom_stride, float angle_threshold,
                     void *vec, void *tip, void *flags, void *stream);
 
+/* Vanishing point of a flow field (additions within ABI v13, csrc/pwc_vanishing.hip): estimate_vanishing_point_from_flow of
+ * pwc_extract_flow_video_vanishpoint.py:93-255 per frame, from vec float [n][gy][gx][2] as pwc_flow_quiver writes it ((dx, dy) in frame
+ * pixels at x = gx*step, y = gy*step; gy = ceil(frame_h / step), gx alike).  fp64 throughout, no fused multiply-add.
+ *   select   dx, dy widened; mag = hypot(dx, dy); a cell is kept when mag >= min_mag; N = number kept.  N <= max_points: all kept cells
+ *            in row-major order.  N > max_points: the kept cells in the sequence of `order` (int32, a permutation of the gy*gx cells;
+ *            entries outside 0 .. gy*gx-1 are skipped), the first max_points of them, in that sequence.  N < 5: status 2.
+ *   pairs    for i < j in the selected order, with (dxn, dyn) = (dx / mag, dy / mag):
+ *                 denom = d1x*d2y - d1y*d2x;  skipped when fabs(denom) < 1e-6;
+ *                 t1 = ((p2x - p1x)*d2y - (p2y - p1y)*d2x) / denom;  ix = p1x + t1*d1x;  iy = p1y + t1*d1y;
+ *            kept when -0.5*W <= ix <= 1.5*W and -0.5*H <= iy <= 1.5*H; fewer than min_pairs kept: status 3.
+ *   votes    np.histogram2d's bins: edges e[k] = k*((hi - lo)/grid) + lo for k < grid and e[grid] = hi, a value in the bin with
+ *            e[k] <= v < e[k+1], v == hi in the last one.  A pair adds llrint((mag_i / M)*(mag_j / M) * 2^40), M the largest selected
+ *            magnitude of the frame, with a 64-bit integer atomic: the histogram has the same bits on every run.
+ *   best     arg-max over gx*grid + gy, the lowest index on a tie; not positive: status 4.  centre = 0.5*(e[g] + e[g+1]) per axis;
+ *            prob = best / (total + 1e-9 * 2^40 / M^2), the reference's best / (total + 1e-9) in the scaled units.
+ *   refine   n = (-dyn, dxn), c = nx*x + ny*y, dist = fabs(nx*cxf + ny*cyf - c) with the centre rounded to float and widened (the
+ *            reference's float32 candidate); median of the N distances (mean of the two middle ones for even N); inliers are
+ *            dist < 3*median + 1e-6.  With >= 5 inliers the 2x2 normal equations of n . (v - centre) = c - n . centre over the
+ *            inliers, summed in a fixed order; det not finite or <= 1e-12 * trace^2, or < 5 inliers: the centre stands, status 1.
+ * out_vp double [n][5] = (vx, vy, prob, centre x, centre y), (NaN, NaN, 0, NaN, NaN) for status >= 2; out_info int32 [n][6] = (status,
+ * N used, pairs kept, best gx, best gy, inliers), best = -1 and inliers = 0 for status >= 2, pairs = 0 for status 2.
+ * workspace: device, 8-byte aligned, pwc_vanishing_workspace_bytes(n, gy, gx, grid) = n * (24 + 8*grid^2 + 4096) bytes (-1 for a
+ * geometry the call refuses).  Three launches on `stream`, nothing allocated, no synchronisation.
+ * PWC_EINVAL, nothing launched: a null vec / out_vp / out_info / workspace, step < 1, non-positive sizes, n > 65535, more than 65536
+ * cells, gy / gx not the grid of the frame, grid outside 2..128, max_points outside 5..1024, gy*gx > max_points with a NULL order, a
+ * workspace that is too small.  PWC_EALIGN: vec / out_vp / workspace not 8-byte aligned, order / out_info not 4-byte aligned. */
+int64_t pwc_vanishing_workspace_bytes(int n, int gy, int gx, int grid);
+int pwc_vanishing_point(const void *vec, int n, int gy, int gx, int frame_h, int frame_w, int step, double min_mag, int max_points,
+                        int grid, int min_pairs, const void *order_or_null /* int32 [gy*gx] */, void *out_vp /* double [n][5] */,
+                        void *out_info /* int32 [n][6] */, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* Training batches of KITTI on the device (addition within ABI v13, csrc/pwc_augment.hip): the "reduced augmentation" (small rotation /
  * zoom / squeeze affine), the random crop and the horizontal flip of KittiFlowDataset (data_processing_or.py:228-294) in one launch,
  * from the raw uint8 frames and the ground truth to the (x, flow, valid) train_one_epoch consumes.  Only the crop_h x crop_w window is

@@ -7,6 +7,8 @@ from .flowio import read_flo, save_outputs, write_flo, write_png8_rgb  # noqa: F
 from . import validation  # noqa: F401
 from . import flowviz  # noqa: F401
 from .flowviz import dominant_direction, flow_to_color, quiver_arrows  # noqa: F401
+from . import vanishing  # noqa: F401
+from .vanishing import vanishing_point  # noqa: F401
 from . import augment  # noqa: F401
 from .augment import DeviceAugmenter, augment_batch  # noqa: F401
 from . import augment_full  # noqa: F401

@@ -109,6 +109,8 @@ SIGNATURES = {
     "pwc_flow_color": (c_int, [c_void_p] + [c_int] * 5 + [c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),
     "pwc_flow_quiver": (c_int, [c_void_p] + [c_int] * 5 + [c_int64, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_float,
                                 c_void_p, c_int64, c_float] + [c_void_p] * 4),
+    "pwc_vanishing_workspace_bytes": (c_int64, [c_int] * 4),
+    "pwc_vanishing_point": (c_int, [c_void_p] + [c_int] * 6 + [c_double] + [c_int] * 3 + [c_void_p] * 4 + [c_int64, c_void_p]),
     "pwc_kitti_augment": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 6),
     "pwc_kitti_augment_full": (c_int, [c_void_p, c_void_p, c_int, c_void_p] + [c_int] * 5 + [c_void_p] * 6),
     "pwc_optim_chunk_elems": (c_int, []),

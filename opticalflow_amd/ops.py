@@ -657,7 +657,65 @@ def flow_quiver(flow: torch.Tensor, frame_h: int, frame_w: int, step: int, vec_s
     return vec, tip, flags
 
 
-AUGMENT_RECORD_BYTES = 88      # sizeof(pwc_augment_params): six fp64, four fp32, six int32
+def vanishing_workspace_bytes(n: int, gy: int, gx: int, grid: int = 64) -> int:
+    return _query_bytes(_lib.load().pwc_vanishing_workspace_bytes(int(n), int(gy), int(gx), int(grid)), "vanishing-point")
+
+
+def vanishing_point(vec: torch.Tensor, frame_h: int, frame_w: int, step: int, min_mag: float = 1.0, max_points: int = 300,
+                    grid: int = 64, min_pairs: int = 50, order: Optional[torch.Tensor] = None,
+                    out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None, workspace: Optional[torch.Tensor] = None):
+    """(vp float64 [n,5], info int32 [n,6]) of pwc_vanishing_point: per frame (vx, vy, prob, centre x, centre y) and (status, N used,
+    pairs kept, best gx, best gy, inliers) from the arrow grid vec float32 [n,Gy,Gx,2] of flow_quiver for the same frame and step.
+    status 0 refined, 1 bin centre kept, 2 fewer than 5 vectors, 3 fewer than min_pairs intersections, 4 empty histogram; the vp row
+    of a status >= 2 is (NaN, NaN, 0, NaN, NaN).  order: int32 permutation of the Gy*Gx cells on the device, required when there are
+    more cells than max_points (it decides which kept cells are used when more than max_points are kept).  vec must be contiguous: a
+    strided view is refused, not copied.  workspace: optional device tensor of vanishing_workspace_bytes(n, Gy, Gx, grid) bytes.
+    Device tensors only, no host synchronisation, bit-reproducible."""
+    frame_h, frame_w, step, max_points, grid, min_pairs = int(frame_h), int(frame_w), int(step), int(max_points), int(grid), int(min_pairs)
+    if frame_h < 1 or frame_w < 1:
+        raise ValueError("frame size must be positive, got %dx%d" % (frame_h, frame_w))
+    if step < 1:
+        raise ValueError("step must be >= 1, got %d" % step)
+    if not 5 <= max_points <= 1024:
+        raise ValueError("max_points must be in 5..1024, got %d" % max_points)
+    if not 2 <= grid <= 128:
+        raise ValueError("grid must be in 2..128, got %d" % grid)
+    gy, gx = (frame_h + step - 1) // step, (frame_w + step - 1) // step
+    if gy * gx > 65536:
+        raise ValueError("%dx%d cells, at most 65536" % (gy, gx))
+    if vec.dim() != 4 or tuple(vec.shape[1:]) != (gy, gx, 2) or vec.shape[0] < 1:
+        raise ValueError("vec must be [n,%d,%d,2] for a %dx%d frame at step %d, got %s" % (gy, gx, frame_h, frame_w, step, tuple(vec.shape)))
+    if vec.dtype != torch.float32:
+        raise TypeError("vec must be float32, got %s" % vec.dtype)
+    _require_device(vec, "vec")
+    if not vec.is_contiguous():
+        raise ValueError("vec must be contiguous (strides %s for shape %s); it is not copied" % (vec.stride(), tuple(vec.shape)))
+    n, dev = vec.shape[0], vec.device
+    if order is None:
+        if gy * gx > max_points:
+            raise ValueError("%d cells can exceed max_points %d: pass an order table" % (gy * gx, max_points))
+        op = None
+    else:
+        op = _table_arg(order, torch.int32, gy * gx, dev, "order")
+    o = out if out is not None else (None, None)
+    if len(o) != 2:
+        raise ValueError("out must be (vp, info)")
+    vp = _out_arg(o[0], (n, 5), torch.float64, dev, contiguous=True)
+    info = _out_arg(o[1], (n, 6), torch.int32, dev, contiguous=True)
+    need = vanishing_workspace_bytes(n, gy, gx, grid)
+    if workspace is None:
+        workspace, _ = _scratch(need, dev)
+    wp, wb = _workspace_args(workspace, vec)
+    if wb < need:
+        raise ValueError("workspace has %d bytes, vanishing_point needs %d" % (wb, need))
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_vanishing_point(vec.data_ptr(), n, gy, gx, frame_h, frame_w, step, float(min_mag), max_points, grid, min_pairs,
+                                             op, vp.data_ptr(), info.data_ptr(), wp, wb, _stream(vec))
+    check(rc, "pwc_vanishing_point")
+    return vp, info
+
+
+AUGMENT_RECORD_BYTES = 88     # sizeof(pwc_augment_params): six fp64, four fp32, six int32
 AUGMENT_FULL_RECORD_BYTES = 128     # sizeof(pwc_augment_full_params): eight fp64, one fp32, eight uint16, eleven int32
 AUGMENT_FULL_MAX_SHIFT = 32767      # PWC_AUGMENT_FULL_MAX_SHIFT
 
