@@ -139,6 +139,28 @@ def _mask_arg(mask: Optional[torch.Tensor], B: int, H: int, W: int, device, rule
     return m, u8, H * W
 
 
+def _kitti_gt_arg(gt: torch.Tensor, valid: Optional[torch.Tensor], n: int, H: int, W: int, device) -> Tuple[int, Optional[torch.Tensor]]:
+    """The two forms of KITTI ground truth -> (gt_kind, valid as the kernels read it).  torch.uint16 [n,H,W,3] is the flow PNG's
+    samples (R G B; validity is the blue sample, so `valid` must be None): kind 1.  float32 [n,2,H,W] are flow planes with `valid`
+    None / bool / uint8 [n,H,W] (bool is returned as its bytes): kind 0.  Everything is contiguous and on `device`."""
+    if gt.dtype == torch.uint16:
+        kind, want = 1, (n, H, W, 3)
+        if valid is not None:
+            raise ValueError("valid must be None with uint16 ground truth (the blue sample is the validity)")
+    elif gt.dtype == torch.float32:
+        kind, want = 0, (n, 2, H, W)
+        if valid is not None:
+            if valid.dtype == torch.bool:
+                valid = valid.view(torch.uint8)
+            if valid.dtype != torch.uint8 or tuple(valid.shape) != (n, H, W) or valid.device != device or not valid.is_contiguous():
+                raise ValueError("valid must be a contiguous bool / uint8 %s tensor on %s" % ((n, H, W), device))
+    else:
+        raise ValueError("gt must be torch.uint16 [n,H,W,3] or float32 [n,2,H,W], got %s" % gt.dtype)
+    if tuple(gt.shape) != want or gt.device != device or not gt.is_contiguous():
+        raise ValueError("gt must be contiguous %s %s on %s, got %s on %s" % (gt.dtype, want, device, tuple(gt.shape), gt.device))
+    return kind, valid
+
+
 def _table_arg(t: torch.Tensor, dtype, min_numel: int, device, name: str) -> int:
     """Device pointer of a contiguous table of at least min_numel elements of this dtype on this device (the kernels trust its
     contents; its placement is checked here)."""

@@ -94,20 +94,22 @@ def sample_params(sizes: Sequence[Tuple[int, int]], crop_hw: Tuple[int, int] = (
     return p
 
 
-def check_params(params: np.ndarray, n: int, slot_hw: Tuple[int, int], crop_hw: Tuple[int, int]) -> np.ndarray:
-    """The records as a contiguous PARAMS_DTYPE array after the checks the kernel repeats on the device (there a record that fails is
-    answered with zeros and a status flag; here it is a ValueError before anything is uploaded)."""
+def check_params(params: np.ndarray, n: int, slot_hw: Tuple[int, int], crop_hw: Tuple[int, int], dtype: np.dtype = PARAMS_DTYPE,
+                 too_small: str = " (the reference's upsize branch is not provided)") -> np.ndarray:
+    """The records as a contiguous array of `dtype` after the checks both kernels repeat on the device (there a record that fails is
+    answered with zeros and a status flag; here it is a ValueError before anything is uploaded): dtype and shape, the sample fits its
+    slot, the crop fits the sample, the crop origin keeps the window inside it.  `too_small` ends the message about a frame smaller
+    than the crop.  augment_full.check_full_params adds the checks of its own record."""
     p = np.ascontiguousarray(params)
-    if p.dtype != PARAMS_DTYPE or p.shape != (n,):
-        raise ValueError("params must be %d records of augment.PARAMS_DTYPE, got %s %s" % (n, p.dtype, p.shape))
+    if p.dtype != dtype or p.shape != (n,):
+        raise ValueError("params must be %d records of the %d-byte parameter dtype, got %s %s" % (n, dtype.itemsize, p.dtype, p.shape))
     (Hs, Ws), (ch, cw) = slot_hw, crop_hw
     for b, r in enumerate(p):
         H, W = int(r["h"]), int(r["w"])
         if not (1 <= H <= Hs and 1 <= W <= Ws):
             raise ValueError("sample %d: size %dx%d does not fit the %dx%d slot" % (b, H, W, Hs, Ws))
         if ch > H or cw > W:
-            raise ValueError("sample %d: a %dx%d frame is smaller than the %dx%d crop (the reference's upsize branch is not provided)"
-                             % (b, H, W, ch, cw))
+            raise ValueError("sample %d: a %dx%d frame is smaller than the %dx%d crop%s" % (b, H, W, ch, cw, too_small))
         if not (0 <= int(r["y0"]) <= H - ch and 0 <= int(r["x0"]) <= W - cw):
             raise ValueError("sample %d: crop origin (%d, %d) outside [0, %d] x [0, %d]" % (b, r["y0"], r["x0"], H - ch, W - cw))
     return p
@@ -164,7 +166,20 @@ def pack_slots(samples, slot_hw: Tuple[int, int], gt_kind: int, frames=None, gt=
 
 
 def _params_tensor(p: np.ndarray) -> torch.Tensor:
-    return torch.from_numpy(p.view(np.uint8).reshape(p.shape[0], PARAMS_DTYPE.itemsize))
+    return torch.from_numpy(p.view(np.uint8).reshape(p.shape[0], p.dtype.itemsize))
+
+
+def _augment_batch(op, check, pairs_u8, gt, valid, params, crop_hw, out, return_status):
+    """augment_batch and augment_full.augment_full_batch: validate the host records with `check`, upload them, launch `op`."""
+    _require_device(pairs_u8, "pairs_u8")
+    if pairs_u8.dim() != 5:
+        raise ValueError("pairs_u8 must be uint8 [n,2,Hs,Ws,3], got %s" % (tuple(pairs_u8.shape),))
+    n, _, Hs, Ws, _ = pairs_u8.shape
+    crop_hw = (int(crop_hw[0]), int(crop_hw[1]))
+    p = check(params, n, (Hs, Ws), crop_hw)
+    pd = _params_tensor(p).to(pairs_u8.device, non_blocking=True)
+    x, flow, v, status = op(pairs_u8, gt, pd, crop_hw, valid=valid, out=out)
+    return (x, flow, v, status) if return_status else (x, flow, v)
 
 
 def augment_batch(pairs_u8: torch.Tensor, gt: torch.Tensor, valid: Optional[torch.Tensor], params: np.ndarray,
@@ -173,31 +188,26 @@ def augment_batch(pairs_u8: torch.Tensor, gt: torch.Tensor, valid: Optional[torc
     [n,2,Hs,Ws,3], gt torch.uint16 [n,Hs,Ws,3] (valid None) or float32 [n,2,Hs,Ws] with valid None / bool / uint8 [n,Hs,Ws] (layout:
     pack_slots).  params: PARAMS_DTYPE records on the host (sample_params), validated here and uploaded.  return_status=True adds the
     kernel's int32 [n] status (all zero after the host checks)."""
-    _require_device(pairs_u8, "pairs_u8")
-    if pairs_u8.dim() != 5:
-        raise ValueError("pairs_u8 must be uint8 [n,2,Hs,Ws,3], got %s" % (tuple(pairs_u8.shape),))
-    n, _, Hs, Ws, _ = pairs_u8.shape
-    crop_hw = (int(crop_hw[0]), int(crop_hw[1]))
-    p = check_params(params, n, (Hs, Ws), crop_hw)
-    pd = _params_tensor(p).to(pairs_u8.device, non_blocking=True)
-    x, flow, v, status = ops.kitti_augment(pairs_u8, gt, pd, crop_hw, valid=valid, out=out)
-    return (x, flow, v, status) if return_status else (x, flow, v)
+    return _augment_batch(ops.kitti_augment, check_params, pairs_u8, gt, valid, params, crop_hw, out, return_status)
 
 
-class DeviceAugmenter:
-    """The training loop's data path: host samples of differing sizes in, the device batch (x, flow_gt, valid) out.
+class StagedAugmenter:
+    """The staging driver of both augmentation operators: host samples of differing sizes in, the device batch out.
 
     Pinned staging, the device slots, the parameter buffer and the outputs are allocated once for `batch` samples of at most
     `max_hw`; `__call__(samples, params=None)` copies the samples into the staging slots (pack_slots), starts the uploads on the
     current stream, launches the kernel behind them and returns views of the output tensors, which the next call overwrites.  Nothing
     synchronises except the wait for the previous upload before the staging memory is rewritten.  gt_kind 1 takes (img1, img2, png
     uint16 [H,W,3]) samples, gt_kind 0 (img1, img2, flow float32 [H,W,2], valid [H,W] or None).  `stage`, `upload` and `run` are the three
-    steps of a call; `run` alone may be captured in a graph and replayed after each `stage` + `upload`."""
+    steps of a call; `run` alone may be captured in a graph and replayed after each `stage` + `upload`.
+
+    A subclass states `dtype` (the record), `third` (the name of its third output, the attribute next to `x`, `flow` and `status`),
+    `sample(sizes)` and `check(params, n)` (how records are drawn and checked) and `op` (what `run` launches)."""
 
     def __init__(self, device, batch: int, max_hw: Tuple[int, int], crop_hw: Tuple[int, int] = (320, 896), gt_kind: int = 1):
         self.device = torch.device(device)
         if self.device.type != "cuda":
-            raise ops.PwcHipError("DeviceAugmenter needs a GPU device, got %s: there is no CPU fallback" % (self.device,))
+            raise ops.PwcHipError("%s needs a GPU device, got %s: there is no CPU fallback" % (type(self).__name__, self.device))
         Hs, Ws = int(max_hw[0]), int(max_hw[1])
         ch, cw = int(crop_hw[0]), int(crop_hw[1])
         if batch < 1 or not (1 <= ch <= Hs and 1 <= cw <= Ws):
@@ -207,19 +217,20 @@ class DeviceAugmenter:
         self.batch, self.slot_hw, self.crop_hw, self.gt_kind = batch, (Hs, Ws), (ch, cw), gt_kind
         shapes = [((batch, 2, Hs, Ws, 3), torch.uint8),
                   ((batch, Hs, Ws, 3), torch.uint16) if gt_kind == 1 else ((batch, 2, Hs, Ws), torch.float32),
-                  ((batch, Hs, Ws), torch.uint8), ((batch, PARAMS_DTYPE.itemsize), torch.uint8)]
+                  ((batch, Hs, Ws), torch.uint8), ((batch, self.dtype.itemsize), torch.uint8)]
         self._host = [torch.zeros(s, dtype=d).pin_memory() for s, d in shapes]
         self._views = [t.numpy() for t in self._host]
         self._dev = [torch.zeros(s, dtype=d, device=self.device) for s, d in shapes]
         self.x = torch.empty((batch, 6, ch, cw), dtype=torch.float32, device=self.device)
         self.flow = torch.empty((batch, 2, ch, cw), dtype=torch.float32, device=self.device)
-        self.valid = torch.empty((batch, 1, ch, cw), dtype=torch.float32, device=self.device)
+        self._third = torch.empty((batch, 1, ch, cw), dtype=torch.float32, device=self.device)
+        setattr(self, self.third, self._third)
         self.status = torch.zeros(batch, dtype=torch.int32, device=self.device)
         self._uploaded = None
         self._n, self._with_valid = 0, False
 
     def stage(self, samples, params: Optional[np.ndarray] = None) -> np.ndarray:
-        """Fill the pinned staging memory from the host samples and their records (drawn with sample_params when None)."""
+        """Fill the pinned staging memory from the host samples and their records (drawn with `sample` when None)."""
         n = len(samples)
         if not 1 <= n <= self.batch:
             raise ValueError("expected 1..%d samples, got %d" % (self.batch, n))
@@ -229,8 +240,8 @@ class DeviceAugmenter:
         fr, gt, va, _ = self._views
         _, _, v, sizes = pack_slots(samples, self.slot_hw, self.gt_kind, frames=fr[:n], gt=gt[:n], valid=va[:n])
         if params is None:
-            params = sample_params(sizes, self.crop_hw)
-        p = check_params(params, n, self.slot_hw, self.crop_hw)
+            params = self.sample(sizes)
+        p = self.check(params, n)
         for b, (H, W) in enumerate(sizes):
             if (int(p[b]["h"]), int(p[b]["w"])) != (H, W):
                 raise ValueError("sample %d is %dx%d but its record says %dx%d" % (b, H, W, p[b]["h"], p[b]["w"]))
@@ -242,7 +253,7 @@ class DeviceAugmenter:
         """Start the copies of what `stage` left to the device slots on the current stream."""
         n = self._n
         if n < 1:
-            raise RuntimeError("DeviceAugmenter.upload before stage")
+            raise RuntimeError("%s.upload before stage" % type(self).__name__)
         use = (0, 1, 3) + ((2,) if self._with_valid else ())
         with torch.cuda.device(self.device):
             for i in use:
@@ -251,17 +262,30 @@ class DeviceAugmenter:
             self._uploaded.record()
 
     def run(self):
-        """The kernel alone, on the device slots as they are, on the current stream -> (x, flow, valid) views of the n staged samples.
-        Nothing is allocated, so a graph may capture it and be replayed after each stage + upload of a batch of the same n."""
+        """The kernel alone, on the device slots as they are, on the current stream -> views of the n staged samples in (x, flow, third
+        output).  Nothing is allocated, so a graph may capture it and be replayed after each stage + upload of a batch of the same n."""
         n = self._n
         if n < 1:
-            raise RuntimeError("DeviceAugmenter.run before stage")
+            raise RuntimeError("%s.run before stage" % type(self).__name__)
         fr, gt, va, pr = self._dev
-        ops.kitti_augment(fr[:n], gt[:n], pr[:n], self.crop_hw, valid=va[:n] if self._with_valid else None,
-                          out=(self.x[:n], self.flow[:n], self.valid[:n]), status=self.status[:n])
-        return self.x[:n], self.flow[:n], self.valid[:n]
+        out = (self.x[:n], self.flow[:n], self._third[:n])
+        self.op(fr[:n], gt[:n], pr[:n], self.crop_hw, valid=va[:n] if self._with_valid else None, out=out, status=self.status[:n])
+        return out
 
     def __call__(self, samples, params: Optional[np.ndarray] = None):
         self.stage(samples, params)
         self.upload()
         return self.run()
+
+
+class DeviceAugmenter(StagedAugmenter):
+    """The training loop's data path (train.py): host samples in, the device batch (x, flow_gt, valid) out, records drawn with
+    sample_params.  Constructor, steps and attributes: StagedAugmenter."""
+
+    dtype, third, op = PARAMS_DTYPE, "valid", staticmethod(ops.kitti_augment)
+
+    def sample(self, sizes):
+        return sample_params(sizes, self.crop_hw)
+
+    def check(self, params, n):
+        return check_params(params, n, self.slot_hw, self.crop_hw)

@@ -18,8 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from ._args import _require_device
-from .augment import invert_affine, pack_slots
+from .augment import StagedAugmenter, _augment_batch, check_params, invert_affine
 
 # pwc_augment_full_params
 FULL_PARAMS_DTYPE = np.dtype([("m", "<f8", (6,)), ("cs", "<f8", (2,)), ("gain", "<f4"), ("wk", "<u2", (7,)), ("ksize", "<u2"),
@@ -131,20 +130,10 @@ def sample_full_params(sizes: Sequence[Tuple[int, int]], crop_hw: Tuple[int, int
 
 
 def check_full_params(params: np.ndarray, n: int, slot_hw: Tuple[int, int], crop_hw: Tuple[int, int]) -> np.ndarray:
-    """The records as a contiguous FULL_PARAMS_DTYPE array after the checks the kernel repeats on the device (there a record that fails
-    is answered with zeros and a status flag; here it is a ValueError before anything is uploaded)."""
-    p = np.ascontiguousarray(params)
-    if p.dtype != FULL_PARAMS_DTYPE or p.shape != (n,):
-        raise ValueError("params must be %d records of augment_full.FULL_PARAMS_DTYPE, got %s %s" % (n, p.dtype, p.shape))
-    (Hs, Ws), (ch, cw) = slot_hw, crop_hw
+    """The records as a contiguous FULL_PARAMS_DTYPE array after the checks the kernel repeats on the device: those of
+    augment.check_params, then the shift range, the tap count and the weight sum."""
+    p = check_params(params, n, slot_hw, crop_hw, dtype=FULL_PARAMS_DTYPE, too_small="")
     for b, r in enumerate(p):
-        H, W = int(r["h"]), int(r["w"])
-        if not (1 <= H <= Hs and 1 <= W <= Ws):
-            raise ValueError("sample %d: size %dx%d does not fit the %dx%d slot" % (b, H, W, Hs, Ws))
-        if ch > H or cw > W:
-            raise ValueError("sample %d: a %dx%d frame is smaller than the %dx%d crop" % (b, H, W, ch, cw))
-        if not (0 <= int(r["y0"]) <= H - ch and 0 <= int(r["x0"]) <= W - cw):
-            raise ValueError("sample %d: crop origin (%d, %d) outside [0, %d] x [0, %d]" % (b, r["y0"], r["x0"], H - ch, W - cw))
         if r["trans"] and (abs(int(r["tx"])) > MAX_SHIFT or abs(int(r["ty"])) > MAX_SHIFT):
             raise ValueError("sample %d: shift (%d, %d) beyond +-%d" % (b, r["tx"], r["ty"], MAX_SHIFT))
         if r["blur"]:
@@ -156,101 +145,27 @@ def check_full_params(params: np.ndarray, n: int, slot_hw: Tuple[int, int], crop
     return p
 
 
-def _params_tensor(p: np.ndarray) -> torch.Tensor:
-    return torch.from_numpy(p.view(np.uint8).reshape(p.shape[0], FULL_PARAMS_DTYPE.itemsize))
-
-
 def augment_full_batch(pairs_u8: torch.Tensor, gt: torch.Tensor, valid: Optional[torch.Tensor], params: np.ndarray,
                        crop_hw: Tuple[int, int] = (320, 896), out=None, return_status: bool = False):
     """(x [n,6,ch,cw], flow [n,2,ch,cw], mask [n,1,ch,cw]) float32 on the device from slot tensors already there (layout: augment.pack_slots,
     arguments: augment.augment_batch).  params: FULL_PARAMS_DTYPE records on the host (sample_full_params), validated here and uploaded.
     The mask is fractional after a rotation, as the reference's.  return_status=True adds the kernel's int32 [n] status."""
-    _require_device(pairs_u8, "pairs_u8")
-    if pairs_u8.dim() != 5:
-        raise ValueError("pairs_u8 must be uint8 [n,2,Hs,Ws,3], got %s" % (tuple(pairs_u8.shape),))
-    n, _, Hs, Ws, _ = pairs_u8.shape
-    crop_hw = (int(crop_hw[0]), int(crop_hw[1]))
-    p = check_full_params(params, n, (Hs, Ws), crop_hw)
-    pd = _params_tensor(p).to(pairs_u8.device, non_blocking=True)
-    x, flow, m, status = ops.kitti_augment_full(pairs_u8, gt, pd, crop_hw, valid=valid, out=out)
-    return (x, flow, m, status) if return_status else (x, flow, m)
+    return _augment_batch(ops.kitti_augment_full, check_full_params, pairs_u8, gt, valid, params, crop_hw, out, return_status)
 
 
-class DeviceFullAugmenter:
-    """train2.py's collate_fn on the device: host samples of differing sizes in, the device batch (x, flow, mask) out.  The contract is
-    augment.DeviceAugmenter's: pinned staging, device slots, the parameter buffer and the outputs are allocated once; `stage` fills the
-    staging memory (records drawn with sample_full_params when None), `upload` starts the copies on the current stream, `run` launches
-    the kernel, allocates nothing and may be captured in a graph; `__call__` does the three.  `augment=False` draws only the crop."""
+class DeviceFullAugmenter(StagedAugmenter):
+    """train2.py's collate_fn on the device: host samples in, the device batch (x, flow, mask) out, records drawn with
+    sample_full_params; `augment=False` draws only the crop.  Constructor, steps and attributes: augment.StagedAugmenter."""
+
+    dtype, third, op = FULL_PARAMS_DTYPE, "mask", staticmethod(ops.kitti_augment_full)
 
     def __init__(self, device, batch: int, max_hw: Tuple[int, int], crop_hw: Tuple[int, int] = (320, 896), gt_kind: int = 1,
                  augment: bool = True):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise ops.PwcHipError("DeviceFullAugmenter needs a GPU device, got %s: there is no CPU fallback" % (self.device,))
-        Hs, Ws = int(max_hw[0]), int(max_hw[1])
-        ch, cw = int(crop_hw[0]), int(crop_hw[1])
-        if batch < 1 or not (1 <= ch <= Hs and 1 <= cw <= Ws):
-            raise ValueError("crop %dx%d does not fit the %dx%d slot (or the batch is empty)" % (ch, cw, Hs, Ws))
-        if gt_kind not in (0, 1):
-            raise ValueError("gt_kind must be 0 or 1, got %r" % (gt_kind,))
-        self.batch, self.slot_hw, self.crop_hw, self.gt_kind, self.augment = batch, (Hs, Ws), (ch, cw), gt_kind, bool(augment)
-        shapes = [((batch, 2, Hs, Ws, 3), torch.uint8),
-                  ((batch, Hs, Ws, 3), torch.uint16) if gt_kind == 1 else ((batch, 2, Hs, Ws), torch.float32),
-                  ((batch, Hs, Ws), torch.uint8), ((batch, FULL_PARAMS_DTYPE.itemsize), torch.uint8)]
-        self._host = [torch.zeros(s, dtype=d).pin_memory() for s, d in shapes]
-        self._views = [t.numpy() for t in self._host]
-        self._dev = [torch.zeros(s, dtype=d, device=self.device) for s, d in shapes]
-        self.x = torch.empty((batch, 6, ch, cw), dtype=torch.float32, device=self.device)
-        self.flow = torch.empty((batch, 2, ch, cw), dtype=torch.float32, device=self.device)
-        self.mask = torch.empty((batch, 1, ch, cw), dtype=torch.float32, device=self.device)
-        self.status = torch.zeros(batch, dtype=torch.int32, device=self.device)
-        self._uploaded = None
-        self._n, self._with_valid = 0, False
+        super().__init__(device, batch, max_hw, crop_hw, gt_kind)
+        self.augment = bool(augment)
 
-    def stage(self, samples, params: Optional[np.ndarray] = None) -> np.ndarray:
-        """Fill the pinned staging memory from the host samples and their records (drawn with sample_full_params when None)."""
-        n = len(samples)
-        if not 1 <= n <= self.batch:
-            raise ValueError("expected 1..%d samples, got %d" % (self.batch, n))
-        if self._uploaded is not None:
-            self._uploaded.synchronize()           # the copy that last read the staging memory must be done before it is rewritten
-            self._uploaded = None
-        fr, gt, va, _ = self._views
-        _, _, v, sizes = pack_slots(samples, self.slot_hw, self.gt_kind, frames=fr[:n], gt=gt[:n], valid=va[:n])
-        if params is None:
-            params = sample_full_params(sizes, self.crop_hw, augment=self.augment)
-        p = check_full_params(params, n, self.slot_hw, self.crop_hw)
-        for b, (H, W) in enumerate(sizes):
-            if (int(p[b]["h"]), int(p[b]["w"])) != (H, W):
-                raise ValueError("sample %d is %dx%d but its record says %dx%d" % (b, H, W, p[b]["h"], p[b]["w"]))
-        np.copyto(self._views[3][:n], p.view(np.uint8).reshape(n, -1))
-        self._n, self._with_valid = n, v is not None
-        return p
+    def sample(self, sizes):
+        return sample_full_params(sizes, self.crop_hw, augment=self.augment)
 
-    def upload(self) -> None:
-        """Start the copies of what `stage` left to the device slots on the current stream."""
-        n = self._n
-        if n < 1:
-            raise RuntimeError("DeviceFullAugmenter.upload before stage")
-        use = (0, 1, 3) + ((2,) if self._with_valid else ())
-        with torch.cuda.device(self.device):
-            for i in use:
-                self._dev[i][:n].copy_(self._host[i][:n], non_blocking=True)
-            self._uploaded = torch.cuda.Event()
-            self._uploaded.record()
-
-    def run(self):
-        """The kernel alone, on the device slots as they are, on the current stream -> (x, flow, mask) views of the n staged samples.
-        Nothing is allocated, so a graph may capture it and be replayed after each stage + upload of a batch of the same n."""
-        n = self._n
-        if n < 1:
-            raise RuntimeError("DeviceFullAugmenter.run before stage")
-        fr, gt, va, pr = self._dev
-        ops.kitti_augment_full(fr[:n], gt[:n], pr[:n], self.crop_hw, valid=va[:n] if self._with_valid else None,
-                               out=(self.x[:n], self.flow[:n], self.mask[:n]), status=self.status[:n])
-        return self.x[:n], self.flow[:n], self.mask[:n]
-
-    def __call__(self, samples, params: Optional[np.ndarray] = None):
-        self.stage(samples, params)
-        self.upload()
-        return self.run()
+    def check(self, params, n):
+        return check_full_params(params, n, self.slot_hw, self.crop_hw)

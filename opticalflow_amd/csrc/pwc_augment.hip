@@ -13,32 +13,21 @@
 // Bounds: a per-sample record is checked by the kernel before anything is read (the sample's outputs become zeros and status 1 when
 // it fails); with a record that passes, the warp == 0 read position lies in [0, h) x [0, w) by the crop-origin check and every
 // warped tap index is folded into [0, len) by reflect101 whatever the matrix holds, so no record can become an out-of-bounds gather.
-#include "pwc_augment_taps.h"
+#include "pwc_augment_common.h"
 
 namespace {
 
 using namespace pwc_aug;
 static_assert(sizeof(pwc_augment_params) == 88, "augment parameter record");
 
-struct Args {
-    const uint8_t *frames;
-    const void *gt;
-    const uint8_t *valid;
-    const pwc_augment_params *params;
-    float *x, *flow, *vout;
-    int *status;
-    int Hs, Ws, crop_h, crop_w, gt_kind;
-};
-
 template <bool VEC>
-__global__ __launch_bounds__(kThreads) void kitti_augment_kernel(Args a) {
+__global__ __launch_bounds__(kThreads) void kitti_augment_kernel(Args<pwc_augment_params> a) {
     const int tid = threadIdx.x, b = blockIdx.z;
     const int y = blockIdx.y * kTH + tid / kLanesX;
     const int x0 = blockIdx.x * kTW + (tid % kLanesX) * kPix;
     const pwc_augment_params P = a.params[b];
     const int H = P.h, W = P.w;
-    const bool bad = H < 1 || H > a.Hs || W < 1 || W > a.Ws || a.crop_h > H || a.crop_w > W || P.y0 < 0 || P.y0 > H - a.crop_h ||
-                     P.x0 < 0 || P.x0 > W - a.crop_w;
+    const bool bad = bad_geometry(P, a.Hs, a.Ws, a.crop_h, a.crop_w);
     if (tid == 0 && blockIdx.x == 0 && blockIdx.y == 0) a.status[b] = bad ? 1 : 0;
     if (y >= a.crop_h || x0 >= a.crop_w) return;
 
@@ -49,13 +38,10 @@ __global__ __launch_bounds__(kThreads) void kitti_augment_kernel(Args a) {
         for (int k = 0; k < kPix; ++k) out[c][k] = 0.0f;
 
     if (!bad) {
-        const int64_t slot = (int64_t)a.Hs * a.Ws;
-        const uint8_t *f1 = a.frames + (int64_t)b * 2 * slot * 3, *f2 = f1 + slot * 3;
-        Gt g;
-        g.png = a.gt_kind == 1 ? static_cast<const uint16_t *>(a.gt) + (int64_t)b * slot * 3 : nullptr;
-        g.fu = static_cast<const float *>(a.gt) + (int64_t)b * 2 * slot;
-        g.fv = g.fu + slot;
-        g.valid = a.valid ? a.valid + (int64_t)b * slot : nullptr;
+        Src S;
+        set_sources(S, a, b);
+        const uint8_t *f1 = S.f1, *f2 = S.f2;
+        const Gt &g = S.g;
         const int Y = P.y0 + y;
         const bool warp = P.warp != 0, flip = P.flip != 0;
         // the row terms of the fixed-point coordinates are the same for the lane's pixels
@@ -112,43 +98,13 @@ __global__ __launch_bounds__(kThreads) void kitti_augment_kernel(Args a) {
         }
     }
 
-    const int64_t plane = (int64_t)a.crop_h * a.crop_w, row = (int64_t)y * a.crop_w;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) store_row<VEC>(a.x + ((int64_t)b * 6 + c) * plane + row, x0, a.crop_w, out[c]);
-    store_row<VEC>(a.flow + ((int64_t)b * 2) * plane + row, x0, a.crop_w, out[6]);
-    store_row<VEC>(a.flow + ((int64_t)b * 2 + 1) * plane + row, x0, a.crop_w, out[7]);
-    store_row<VEC>(a.vout + (int64_t)b * plane + row, x0, a.crop_w, out[8]);
+    store_planes<VEC>(a.x, a.flow, a.vout, a.crop_h, a.crop_w, b, y, x0, out);
 }
 
 }  // namespace
 
 extern "C" int pwc_kitti_augment(const void *frames, const void *gt, int gt_kind, const void *valid, int n, int Hs, int Ws, int crop_h,
                                  int crop_w, const void *params, void *x, void *flow, void *valid_out, void *status, void *stream) {
-    if (!frames || !gt || !params || !x || !flow || !valid_out || !status) PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment: null pointer");
-    if (n <= 0 || Hs <= 0 || Ws <= 0 || crop_h <= 0 || crop_w <= 0)
-        PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment: bad shape n=%d slot=%dx%d crop=%dx%d", n, Hs, Ws, crop_h, crop_w);
-    if (n > 65535 || Hs > 32767 || Ws > 32767) PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment: needs n <= 65535 and a slot of at most 32767 x 32767");
-    if (crop_h > Hs || crop_w > Ws) PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment: crop %dx%d larger than the slot %dx%d", crop_h, crop_w, Hs, Ws);
-    if (gt_kind != 0 && gt_kind != 1) PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment: unknown gt_kind %d (0 = float planes, 1 = uint16 PNG samples)", gt_kind);
-    if (gt_kind == 1 && valid) PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment: gt_kind 1 carries its own validity, valid must be NULL");
-    if (pwc::misaligned({x, flow, valid_out, status}) || pwc::misaligned({gt}, gt_kind == 1 ? 2 : 4))
-        PWC_FAIL(PWC_EALIGN, "pwc_kitti_augment: float / int32 pointers must be 4-byte aligned, a uint16 gt 2-byte aligned");
-    if (pwc::misaligned({params}, 8)) PWC_FAIL(PWC_EALIGN, "pwc_kitti_augment: the parameter buffer must be 8-byte aligned");
-    Args a;
-    a.frames = static_cast<const uint8_t *>(frames);
-    a.gt = gt;
-    a.valid = static_cast<const uint8_t *>(valid);
-    a.params = static_cast<const pwc_augment_params *>(params);
-    a.x = static_cast<float *>(x);
-    a.flow = static_cast<float *>(flow);
-    a.vout = static_cast<float *>(valid_out);
-    a.status = static_cast<int *>(status);
-    a.Hs = Hs; a.Ws = Ws; a.crop_h = crop_h; a.crop_w = crop_w; a.gt_kind = gt_kind;
-    const dim3 grid((crop_w + kTW - 1) / kTW, (crop_h + kTH - 1) / kTH, n);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (crop_w % kPix == 0 && !pwc::misaligned({x, flow, valid_out}, 16))
-        hipLaunchKernelGGL(kitti_augment_kernel<true>, grid, dim3(kThreads), 0, st, a);
-    else
-        hipLaunchKernelGGL(kitti_augment_kernel<false>, grid, dim3(kThreads), 0, st, a);
-    return pwc::check_launch("kitti_augment_kernel");
+    return launch<pwc_augment_params>("pwc_kitti_augment", "kitti_augment_kernel", kitti_augment_kernel<true>, kitti_augment_kernel<false>, frames,
+                                      gt, gt_kind, valid, n, Hs, Ws, crop_h, crop_w, params, x, flow, valid_out, status, stream);
 }

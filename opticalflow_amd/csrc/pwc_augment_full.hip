@@ -17,7 +17,7 @@
 // every window position -- shifted, rotated or a halo -- is folded into [0, crop_h) x [0, crop_w) by reflect_edge / reflect101 whatever
 // the matrix or the shift holds, and the window lies inside the sample by the crop-origin check, so no record becomes an
 // out-of-bounds gather.  The blur weights are read only below ksize <= 7 and must add up to 256, so the uint16 pass cannot overflow.
-#include "pwc_augment_taps.h"
+#include "pwc_augment_common.h"
 
 namespace {
 
@@ -30,21 +30,6 @@ constexpr int kSWp = (kSW + 3) / 4 * 4;                           // rows padded
 constexpr int kRing = kSH * kSW - kTH * kTW;                      // 852 halo positions around the 1024 owned ones
 static_assert(kRing == 2 * kHalo * kSW + 2 * kHalo * kTH, "halo ring");
 static_assert(kSWp / 4 >= kLanesX + 2, "the horizontal pass reads three words per lane");
-
-struct Args {
-    const uint8_t *frames;
-    const void *gt;
-    const uint8_t *valid;
-    const pwc_augment_full_params *params;
-    float *x, *flow, *vout;
-    int *status;
-    int Hs, Ws, crop_h, crop_w, gt_kind;
-};
-
-struct Src {
-    const uint8_t *f1, *f2;
-    Gt g;
-};
 
 __device__ __forceinline__ float blend(float p00, float p01, float p10, float p11, float w00, float w01, float w10, float w11) {
     return ((p00 * w00 + p01 * w01) + p10 * w10) + p11 * w11;
@@ -128,7 +113,7 @@ __device__ __forceinline__ void chain(const Src &S, const pwc_augment_full_param
 }
 
 template <bool VEC>
-__global__ __launch_bounds__(kThreads) void kitti_augment_full_kernel(Args a) {
+__global__ __launch_bounds__(kThreads) void kitti_augment_full_kernel(Args<pwc_augment_full_params> a) {
     __shared__ __align__(16) uint8_t tile8[6][kSH][kSWp];
     __shared__ __align__(16) uint16_t hrow[6][kSH][kTW];
 
@@ -138,8 +123,7 @@ __global__ __launch_bounds__(kThreads) void kitti_augment_full_kernel(Args a) {
     const int ch = a.crop_h, cw = a.crop_w;
     const pwc_augment_full_params P = a.params[b];
     const uint16_t *wk = a.params[b].wk;           // indexed at run time: read from memory, not from the register copy
-    const int H = P.h, W = P.w;
-    bool bad = H < 1 || H > a.Hs || W < 1 || W > a.Ws || ch > H || cw > W || P.y0 < 0 || P.y0 > H - ch || P.x0 < 0 || P.x0 > W - cw;
+    bool bad = bad_geometry(P, a.Hs, a.Ws, ch, cw);
     if (P.trans != 0)
         bad = bad || P.tx < -PWC_AUGMENT_FULL_MAX_SHIFT || P.tx > PWC_AUGMENT_FULL_MAX_SHIFT || P.ty < -PWC_AUGMENT_FULL_MAX_SHIFT ||
               P.ty > PWC_AUGMENT_FULL_MAX_SHIFT;
@@ -172,14 +156,8 @@ __global__ __launch_bounds__(kThreads) void kitti_augment_full_kernel(Args a) {
         for (int k = 0; k < kPix; ++k) out[c][k] = 0.0f;
 
     if (!bad) {                                    // bad and every flag are the same for the whole workgroup
-        const int64_t slot = (int64_t)a.Hs * a.Ws;
         Src S;
-        S.f1 = a.frames + (int64_t)b * 2 * slot * 3;
-        S.f2 = S.f1 + slot * 3;
-        S.g.png = a.gt_kind == 1 ? static_cast<const uint16_t *>(a.gt) + (int64_t)b * slot * 3 : nullptr;
-        S.g.fu = static_cast<const float *>(a.gt) + (int64_t)b * 2 * slot;
-        S.g.fv = S.g.fu + slot;
-        S.g.valid = a.valid ? a.valid + (int64_t)b * slot : nullptr;
+        set_sources(S, a, b);
         float img[6], u = 0.0f, v = 0.0f, m = 0.0f;
 
         if (P.blur == 0) {
@@ -267,46 +245,14 @@ __global__ __launch_bounds__(kThreads) void kitti_augment_full_kernel(Args a) {
     }
     if (!live) return;
 
-    const int64_t plane = (int64_t)ch * cw, row = (int64_t)y * cw;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) store_row<VEC>(a.x + ((int64_t)b * 6 + c) * plane + row, x0, cw, out[c]);
-    store_row<VEC>(a.flow + ((int64_t)b * 2) * plane + row, x0, cw, out[6]);
-    store_row<VEC>(a.flow + ((int64_t)b * 2 + 1) * plane + row, x0, cw, out[7]);
-    store_row<VEC>(a.vout + (int64_t)b * plane + row, x0, cw, out[8]);
+    store_planes<VEC>(a.x, a.flow, a.vout, a.crop_h, a.crop_w, b, y, x0, out);
 }
 
 }  // namespace
 
 extern "C" int pwc_kitti_augment_full(const void *frames, const void *gt, int gt_kind, const void *valid, int n, int Hs, int Ws, int crop_h,
                                       int crop_w, const void *params, void *x, void *flow, void *mask_out, void *status, void *stream) {
-    if (!frames || !gt || !params || !x || !flow || !mask_out || !status) PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment_full: null pointer");
-    if (n <= 0 || Hs <= 0 || Ws <= 0 || crop_h <= 0 || crop_w <= 0)
-        PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment_full: bad shape n=%d slot=%dx%d crop=%dx%d", n, Hs, Ws, crop_h, crop_w);
-    if (n > 65535 || Hs > 32767 || Ws > 32767)
-        PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment_full: needs n <= 65535 and a slot of at most 32767 x 32767");
-    if (crop_h > Hs || crop_w > Ws)
-        PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment_full: crop %dx%d larger than the slot %dx%d", crop_h, crop_w, Hs, Ws);
-    if (gt_kind != 0 && gt_kind != 1)
-        PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment_full: unknown gt_kind %d (0 = float planes, 1 = uint16 PNG samples)", gt_kind);
-    if (gt_kind == 1 && valid) PWC_FAIL(PWC_EINVAL, "pwc_kitti_augment_full: gt_kind 1 carries its own validity, valid must be NULL");
-    if (pwc::misaligned({x, flow, mask_out, status}) || pwc::misaligned({gt}, gt_kind == 1 ? 2 : 4))
-        PWC_FAIL(PWC_EALIGN, "pwc_kitti_augment_full: float / int32 pointers must be 4-byte aligned, a uint16 gt 2-byte aligned");
-    if (pwc::misaligned({params}, 8)) PWC_FAIL(PWC_EALIGN, "pwc_kitti_augment_full: the parameter buffer must be 8-byte aligned");
-    Args a;
-    a.frames = static_cast<const uint8_t *>(frames);
-    a.gt = gt;
-    a.valid = static_cast<const uint8_t *>(valid);
-    a.params = static_cast<const pwc_augment_full_params *>(params);
-    a.x = static_cast<float *>(x);
-    a.flow = static_cast<float *>(flow);
-    a.vout = static_cast<float *>(mask_out);
-    a.status = static_cast<int *>(status);
-    a.Hs = Hs; a.Ws = Ws; a.crop_h = crop_h; a.crop_w = crop_w; a.gt_kind = gt_kind;
-    const dim3 grid((crop_w + kTW - 1) / kTW, (crop_h + kTH - 1) / kTH, n);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (crop_w % kPix == 0 && !pwc::misaligned({x, flow, mask_out}, 16))
-        hipLaunchKernelGGL(kitti_augment_full_kernel<true>, grid, dim3(kThreads), 0, st, a);
-    else
-        hipLaunchKernelGGL(kitti_augment_full_kernel<false>, grid, dim3(kThreads), 0, st, a);
-    return pwc::check_launch("kitti_augment_full_kernel");
+    return launch<pwc_augment_full_params>("pwc_kitti_augment_full", "kitti_augment_full_kernel", kitti_augment_full_kernel<true>,
+                                           kitti_augment_full_kernel<false>, frames, gt, gt_kind, valid, n, Hs, Ws, crop_h, crop_w, params, x,
+                                           flow, mask_out, status, stream);
 }

@@ -16,8 +16,8 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._args import (_bias_arg, _dtype_code, _f32_dense, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr, _query_bytes,
-                    _require_device, _scalar_arg, _scratch, _stream, _table_arg, _workspace_args, densify)
+from ._args import (_bias_arg, _dtype_code, _f32_dense, _kitti_gt_arg, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr,
+                    _query_bytes, _require_device, _scalar_arg, _scratch, _stream, _table_arg, _workspace_args, densify)
 from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F32, PwcHipError, check)
 
 def corr_output_shape(C: int, H: int, W: int, pad_size: int, kernel_size: int, max_displacement: int,
@@ -518,23 +518,7 @@ def kitti_score(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, out_
     dev = flow_q.device
     bsq = _plane_dense(flow_q, "flow_q")
     out_h, out_w = int(out_h), int(out_w)
-    if gt.device != dev or not gt.is_contiguous():
-        raise ValueError("gt must be a contiguous tensor on %s" % dev)
-    if gt.dtype == torch.uint16:
-        kind, want = 1, (n, out_h, out_w, 3)
-        if valid is not None:
-            raise ValueError("valid must be None with uint16 ground truth (the blue sample is the validity)")
-    elif gt.dtype == torch.float32:
-        kind, want = 0, (n, 2, out_h, out_w)
-        if valid is not None:
-            if valid.dtype == torch.bool:
-                valid = valid.view(torch.uint8)
-            if valid.dtype != torch.uint8 or tuple(valid.shape) != (n, out_h, out_w) or valid.device != dev or not valid.is_contiguous():
-                raise ValueError("valid must be a contiguous bool / uint8 %s tensor on %s" % ((n, out_h, out_w), dev))
-    else:
-        raise ValueError("gt must be torch.uint16 [n,H,W,3] or float32 [n,2,H,W], got %s" % gt.dtype)
-    if tuple(gt.shape) != want:
-        raise ValueError("gt must be %s %s, got %s" % (gt.dtype, want, tuple(gt.shape)))
+    kind, valid = _kitti_gt_arg(gt, valid, n, out_h, out_w, dev)
     if flow_out is not None and (tuple(flow_out.shape) != (n, 2, out_h, out_w) or flow_out.dtype != torch.float32 or flow_out.device != dev
                                  or not flow_out.is_contiguous()):
         raise ValueError("flow_out must be contiguous float32 %s on %s" % ((n, 2, out_h, out_w), dev))
@@ -730,21 +714,7 @@ def _kitti_augment_call(symbol: str, record_bytes: int, frames, gt, params, crop
     ch, cw = int(crop_hw[0]), int(crop_hw[1])
     if n < 1 or not (1 <= ch <= Hs and 1 <= cw <= Ws):
         raise ValueError("crop %dx%d does not fit the %dx%d slot (or the batch is empty)" % (ch, cw, Hs, Ws))
-    if gt.dtype == torch.uint16:
-        kind, want = 1, (n, Hs, Ws, 3)
-        if valid is not None:
-            raise ValueError("valid must be None with uint16 ground truth (the blue sample is the validity)")
-    elif gt.dtype == torch.float32:
-        kind, want = 0, (n, 2, Hs, Ws)
-        if valid is not None:
-            if valid.dtype == torch.bool:
-                valid = valid.view(torch.uint8)
-            if valid.dtype != torch.uint8 or tuple(valid.shape) != (n, Hs, Ws) or valid.device != dev or not valid.is_contiguous():
-                raise ValueError("valid must be a contiguous bool / uint8 %s tensor on %s" % ((n, Hs, Ws), dev))
-    else:
-        raise ValueError("gt must be torch.uint16 [n,Hs,Ws,3] or float32 [n,2,Hs,Ws], got %s" % gt.dtype)
-    if tuple(gt.shape) != want or gt.device != dev or not gt.is_contiguous():
-        raise ValueError("gt must be contiguous %s %s on %s, got %s on %s" % (gt.dtype, want, dev, tuple(gt.shape), gt.device))
+    kind, valid = _kitti_gt_arg(gt, valid, n, Hs, Ws, dev)
     if params.dtype != torch.uint8 or tuple(params.shape) != (n, record_bytes) or params.device != dev or not params.is_contiguous():
         raise ValueError("params must be contiguous uint8 %s on %s" % ((n, record_bytes), dev))
     o = out if out is not None else (None, None, None)
