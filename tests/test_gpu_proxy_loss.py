@@ -1,5 +1,8 @@
 """GPU checks of the fused proxy-label loss (csrc/pwc_proxy_loss.hip) against the reference's own float64 results (g8 fixture)
-and, per element, against the fp64 oracle of tests/proxy_loss_oracle.py at training sizes."""
+and, per element, against the fp64 oracle of tests/proxy_loss_oracle.py at training sizes.  Every size here is a multiple of the
+16 x 64 tile or leaves a 32-column tail, every flow is at a quarter of the image (or at its size), C = 3 and the operands are dense;
+tests/test_gpu_proxy_loss_edges.py runs the same oracle off those sizes: one- and two-pixel tile tails, the 2 x 2 extremes,
+non-integer ratios, one and four channels, batch-strided operands, and the gradient per term (tests/proxy_loss_cases.py)."""
 import numpy as np
 import pytest
 import torch
