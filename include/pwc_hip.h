@@ -471,6 +471,39 @@ int pwc_kitti_ingest_u8(const void *pairs_u8, void *x, int n, int H, int W, cons
 int pwc_flow_upsample_f32(const void *flow_q, void *out, int n, int Hq, int Wq, int crop_h, int crop_w, int out_h, int out_w,
                           int64_t q_bstride, void *stream);
 
+/* Pillow-exact bilinear resize (ABI v13 additions, csrc/pwc_pil_resize.hip): transforms.Resize -> ToTensor -> Normalize of
+ * train_pseudo.py:370-374 / train_fundamental.py:567-571 / inference.py:305-309 on 8-bit frames, and resize_flow of inference.py:162-190
+ * on float planes.  Image.resize(..., BILINEAR) is a separable triangle filter whose support widens with the scale factor.  Per axis
+ * with input length I and output length O the HOST makes, in IEEE double (opticalflow_amd/pil_resize.py coeff_tables / fixed_point):
+ *   scale = I / O; fs = max(scale, 1); support = fs; ksize = 2 * ceil(support) + 1; for each output index xx:
+ *   center = (xx + 0.5) * scale; first = max((int)(center - support + 0.5), 0); count = min((int)(center + support + 0.5), I) - first;
+ *   w[t] = tri((t + first - center + 0.5) / fs), tri(v) = 1 - |v| for |v| < 1 else 0, divided by their sum in tap order when it is not 0.
+ * bounds [O][2] int32 = (first, count); coefficients [O][ksize], taps past count zero: float64 w for planes, int32
+ * k = (int)(w * 2^22 + 0.5) for frames.  All tables are DEVICE pointers; the kernels clamp what they hold so that no tap leaves the image.
+ * pwc_pil_resize_frames_u8: frames uint8 [n][H][W][3] (interleaved RGB, dense) -> out_f32 planes of [h][w], and when out_u8 is not
+ *   NULL the resized bytes [n][h][w][3].  sample = clip(0, 255, (2^21 + sum_t src[first + t] * k[t]) >> 22) in int32; the horizontal pass
+ *   first, ROUNDED TO BYTES, the vertical pass on those bytes; out_f32 = lut768[c * 256 + byte] (float [3][256], device: ToTensor and
+ *   Normalize tabulated by the caller).  Frame f is written to out_f32 + (f % out_group) * out_bstride + (f / out_group) * 3 * h * w
+ *   (elements): out_group = n gives [n][3][h][w] with a free batch stride, out_group = n / 2 puts the second half of the frames
+ *   into channels 3..5 of the first half's items (the [B][6][h][w] network input).
+ * pwc_pil_resize_planes_f32: src float [n][c][in_h][in_w] (dense planes, free batch stride in elements) -> dst [n][c][out_h][out_w]
+ *   (dense).  ss = 0.0; ss += (double)src[first + t] * w[t] in tap order, multiply and add separate; (float)ss; horizontal pass first
+ *   with a float intermediate.  factors (device, float [c], may be NULL): dst = (float)ss * factors[channel] in float.
+ * One launch each (a workgroup resamples the source rows of its 16 x 64 output tile horizontally into LDS and takes the vertical pass
+ * from there); neither allocates nor synchronises.  Supported: I <= 8 * O on both axes (a downscale of at most 8, ksize <= 17; any upscale), sizes <= 2^20
+ * (pwc_pil_resize_supported: 1 / 0; pwc_pil_resize_ksize: the ksize of one axis, PWC_EINVAL outside the range).
+ * PWC_EINVAL, nothing launched: a null pointer (out_u8 / factors may be NULL), non-positive sizes or out_group, an unsupported scale,
+ * a ksize that disagrees with the sizes, a batch stride smaller than the tensor, n (frames) or n * c (planes) > 65535.  PWC_EALIGN,
+ * nothing launched: out_f32 / src / dst / bounds / int32 coefficients / lut768 / factors not 4-byte, float64 coefficients not 8-byte aligned. */
+int pwc_pil_resize_ksize(int in_size, int out_size);
+int pwc_pil_resize_supported(int in_h, int in_w, int out_h, int out_w);
+int pwc_pil_resize_frames_u8(const void *frames_u8, void *out_f32, void *out_u8, int n, int H, int W, int h, int w,
+                             const int32_t *xbounds, const int32_t *xcoef, int xksize, const int32_t *ybounds, const int32_t *ycoef,
+                             int yksize, const float *lut768, int64_t out_bstride, int out_group, void *stream);
+int pwc_pil_resize_planes_f32(const void *src, void *dst, int n, int c, int in_h, int in_w, int out_h, int out_w,
+                              const int32_t *xbounds, const double *xcoef, int xksize, const int32_t *ybounds, const double *ycoef,
+                              int yksize, const float *factors, int64_t src_bstride, void *stream);
+
 /* KITTI scoring on the device (ABI v13 additions, csrc/pwc_kitti_score.hip): EPE and Fl-all of inference_kitti.py:94-128
  * (epe_metric / fl_all_metric) straight from the network's quarter-resolution flow, nothing image-sized written unless asked for.
  * flow_q [n][2][Hq][Wq] f32 (dense planes, batch stride in elements).  Per pixel (b, y, x) of the out_h x out_w grid, in fp32 with

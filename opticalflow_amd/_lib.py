@@ -101,6 +101,12 @@ SIGNATURES = {
     "pwc_conv3x3_wino4_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
     "pwc_kitti_ingest_u8": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
     "pwc_flow_upsample_f32": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_void_p]),
+    "pwc_pil_resize_ksize": (c_int, [c_int, c_int]),
+    "pwc_pil_resize_supported": (c_int, [c_int] * 4),
+    "pwc_pil_resize_frames_u8": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_int64, c_int, c_void_p]),
+    "pwc_pil_resize_planes_f32": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
+                                          c_void_p, c_int64, c_void_p]),
     "pwc_kitti_score_workspace_bytes": (c_int64, [c_int] * 3),
     "pwc_kitti_score": (c_int, [c_void_p] + [c_int] * 7 + [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64,
                                 c_void_p, c_void_p]),

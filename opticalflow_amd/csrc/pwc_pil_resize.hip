@@ -1,0 +1,295 @@
+// Pillow-exact bilinear resize on the device (opticalflow_amd/pil_resize.py): the first stage of train_pseudo.py / train_fundamental.py /
+// inference.py (transforms.Resize -> ToTensor -> Normalize on 8-bit RGB frames) and inference.py's resize_flow (mode "F" planes).
+//
+// Pillow's BILINEAR is a separable triangle filter whose support widens with the scale factor.  Per axis the host makes a bounds
+// table [O][2] (first tap, number of taps) and a coefficient table [O][ksize]; the kernels only apply them:
+//   frames : sample = clip8((2^21 + sum_t src[first + t] * k[t]) >> 22) in int32, the horizontal pass first and ROUNDED TO BYTES,
+//            the vertical pass on those bytes, then lut[c][byte] (ToTensor + Normalize as a 3 x 256 float table made with torch).
+//   planes : ss = 0.0; ss += (double)src[first + t] * w[t] in tap order (separate multiply and add: -ffp-contract=off), (float)ss;
+//            horizontal first with a float intermediate; an optional per-channel float factor after the second pass.
+// One launch.  A workgroup owns a 16 x 64 output tile of one image: it resamples the source rows its tile needs (they follow from the
+// vertical bounds of the tile's first and last row) horizontally into LDS and takes the vertical pass from there.  Frames: the
+// source bytes of a batch of rows come in as aligned dwords with the lanes along x (the taps of neighbouring outputs overlap, and a
+// byte load per tap from global memory took 2.2x the time at 1080x1920 -> 384x512), the taps are then byte reads of LDS; the resampled rows are staged as
+// interleaved RGB bytes, so a thread of the vertical pass reads 12 contiguous bytes (4 pixels x 3 channels) per tap and ends with
+// three 16-byte stores, one per output plane.  The LDS of a launch is sized by its scale factors (dynamic), not by the largest one.
+#include <stdint.h>
+#include <math.h>
+
+#include "pwc_common.h"
+
+namespace {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kTH = 16, kTW = 64;          // output tile
+constexpr int kMaxScale = 8;               // supported: in <= 8 * out per axis (an upscale has 3-tap rows whatever its factor)
+constexpr int kMaxK = 2 * kMaxScale + 1;   // ksize at the largest downscale
+// staged rows of a tile: the centres of 16 output rows span 15 * scale <= 120 source rows, the support adds <= 8 on each side and the
+// two roundings of the bounds at most 1 more: 137
+constexpr int kMaxRows = 144;
+constexpr int kPitchB = kTW * 3 + 4;       // frame staging: 192 bytes of a row + one dword, so rows start on different banks
+constexpr int kMaxDim = 1 << 20;
+
+// bounds of a table row as the kernel uses them: whatever the table holds, no tap leaves [0, in)
+__device__ __forceinline__ int2 safe_bounds(const int32_t *__restrict__ b, int i, int in, int ksize) {
+    const int first = min(max(b[2 * i], 0), in - 1);
+    const int cnt = min(min(max(b[2 * i + 1], 0), ksize), in - first);
+    return make_int2(first, cnt);
+}
+
+__device__ __forceinline__ int clip8(int v) { return min(max(v >> 22, 0), 255); }
+
+// unaligned source bytes as aligned dwords: the dword at `p`, and where it is not wholly inside [lo, hi) its inside bytes alone
+__device__ __forceinline__ uint32_t load_dword_within(const uint8_t *p, const uint8_t *lo, const uint8_t *hi) {
+    if (p >= lo && p + 4 <= hi) return *reinterpret_cast<const uint32_t *>(p);
+    uint32_t v = 0;
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+        if (p + i >= lo && p + i < hi) v |= (uint32_t)p[i] << (8 * i);
+    return v;
+}
+
+// dynamic LDS: [rows_cap][kPitchB] horizontally resampled rows of the tile, then [raw_rows][raw_pitch] source bytes of one row batch
+__global__ void __launch_bounds__(256)
+pil_frames_kernel(const uint8_t *__restrict__ src, float *__restrict__ out, uint8_t *__restrict__ out8, int H, int W, int h, int w,
+                  const int32_t *__restrict__ xb, const int32_t *__restrict__ xk, int xks, const int32_t *__restrict__ yb,
+                  const int32_t *__restrict__ yk, int yks, const float *__restrict__ lut, int64_t bso, int group, int vec,
+                  int rows_cap, int raw_pitch, int raw_rows, int64_t src_bytes) {
+    extern __shared__ __attribute__((aligned(16))) uint8_t s_dyn[];
+    __shared__ int32_t s_xk[kTW * kMaxK], s_yk[kTH * kMaxK];
+    __shared__ int2 s_xb[kTW], s_yb[kTH];
+    __shared__ float s_lut[768];
+    uint8_t *s_rows = s_dyn, *s_raw = s_dyn + rows_cap * kPitchB;
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH, f = blockIdx.z;
+    const int tw = min(kTW, w - x0), th = min(kTH, h - y0);
+
+    for (int i = tid; i < 768; i += 256) s_lut[i] = lut[i];
+    if (tid < tw) s_xb[tid] = safe_bounds(xb, x0 + tid, W, xks);
+    if (tid >= 64 && tid < 64 + th) s_yb[tid - 64] = safe_bounds(yb, y0 + tid - 64, H, yks);
+    for (int i = tid; i < tw * xks; i += 256) s_xk[i] = xk[(int64_t)x0 * xks + i];
+    for (int i = tid; i < th * yks; i += 256) s_yk[i] = yk[(int64_t)y0 * yks + i];
+    __syncthreads();
+
+    // source rows of this tile: first tap of its first row .. last tap of its last row (both bounds grow with y), and its source
+    // columns likewise.  A column keeps only the taps a raw row has room for (all of them, with tables the host made).
+    const int r0 = s_yb[0].x;
+    const int rows = min(max(s_yb[th - 1].x + s_yb[th - 1].y - r0, 0), rows_cap);
+    const int xlo = s_xb[0].x;
+    const int2 mine = s_xb[min(tid, tw - 1)];
+    __syncthreads();
+    if (tid < tw) s_xb[tid] = make_int2(max(mine.x - xlo, 0), max(min(mine.y, (raw_pitch - 3) / 3 - max(mine.x - xlo, 0)), 0));
+    __syncthreads();
+    const int span = (s_xb[tw - 1].x + s_xb[tw - 1].y) * 3;      // source bytes of a row, <= raw_pitch - 3
+    const int pd = raw_pitch >> 2;
+    const uint8_t *img = src + (int64_t)f * H * W * 3 + (int64_t)xlo * 3;
+
+    for (int rb = 0; rb < rows; rb += raw_rows) {
+        const int nr = min(raw_rows, rows - rb);
+        // the batch's source bytes as aligned dwords, lanes along x
+        for (int it = tid; it < nr * pd; it += 256) {
+            const int r = it / pd, d = it - r * pd;
+            const uint8_t *row = img + (int64_t)(r0 + rb + r) * W * 3;
+            const int shift = (int)(reinterpret_cast<uintptr_t>(row) & 3);
+            if (4 * d < shift + span)
+                *reinterpret_cast<uint32_t *>(s_raw + r * raw_pitch + 4 * d) = load_dword_within(row - shift + 4 * d, src, src + src_bytes);
+        }
+        __syncthreads();
+        // horizontal pass: one thread = one dword of a staged row = 4 interleaved bytes (x, c) = (j / 3, j % 3)
+        for (int it = tid; it < nr * (kTW * 3 / 4); it += 256) {
+            const int r = it / (kTW * 3 / 4), q = it - r * (kTW * 3 / 4);
+            const int shift = (int)(reinterpret_cast<uintptr_t>(img + (int64_t)(r0 + rb + r) * W * 3) & 3);
+            const uint8_t *row = s_raw + r * raw_pitch + shift;
+            uint32_t packed = 0;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int j = 4 * q + i, xl = j / 3, c = j - 3 * xl;
+                if (xl < tw) {
+                    const int2 b = s_xb[xl];
+                    const uint8_t *p = row + b.x * 3 + c;
+                    const int32_t *k = s_xk + xl * xks;
+                    int ss = 1 << 21;
+                    for (int t = 0; t < b.y; ++t) ss += (int)p[3 * t] * k[t];
+                    packed |= (uint32_t)clip8(ss) << (8 * i);
+                }
+            }
+            *reinterpret_cast<uint32_t *>(s_rows + (rb + r) * kPitchB + 4 * q) = packed;
+        }
+        __syncthreads();
+    }
+
+    // vertical pass: one thread = 4 pixels x 3 channels of one output row
+    const int yl = tid >> 4, xq = tid & 15;
+    if (yl >= th || 4 * xq >= tw) return;
+    const int2 b = s_yb[yl];
+    int ss[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) ss[i] = 1 << 21;
+    for (int t = 0; t < b.y; ++t) {
+        const int r = min(b.x - r0 + t, rows_cap - 1);
+        const uint32_t *p = reinterpret_cast<const uint32_t *>(s_rows + r * kPitchB + 12 * xq);
+        const int k = s_yk[yl * yks + t];
+        const uint32_t d[3] = {p[0], p[1], p[2]};
+#pragma unroll
+        for (int i = 0; i < 12; ++i) ss[i] += (int)((d[i >> 2] >> (8 * (i & 3))) & 255u) * k;
+    }
+    int v[12];
+#pragma unroll
+    for (int i = 0; i < 12; ++i) v[i] = clip8(ss[i]);
+
+    const int y = y0 + yl, x = x0 + 4 * xq;
+    const int b_out = f % group, half = f / group;
+    float *o = out + (int64_t)b_out * bso + ((int64_t)(3 * half) * h + y) * w + x;
+    const int64_t plane = (int64_t)h * w;
+    if (vec) {                                   // w % 4 == 0 and every plane row 16-byte aligned: the quad is whole
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            *reinterpret_cast<f32x4 *>(o + c * plane) =
+                (f32x4){s_lut[c * 256 + v[c]], s_lut[c * 256 + v[3 + c]], s_lut[c * 256 + v[6 + c]], s_lut[c * 256 + v[9 + c]]};
+    } else {
+        for (int px = 0; px < 4 && x + px < w; ++px)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) o[c * plane + px] = s_lut[c * 256 + v[3 * px + c]];
+    }
+    if (out8) {
+        uint8_t *o8 = out8 + (((int64_t)f * h + y) * w + x) * 3;
+        const int nb = 3 * min(4, w - x);
+        for (int i = 0; i < 12; ++i)
+            if (i < nb) o8[i] = (uint8_t)v[i];
+    }
+}
+
+__global__ void __launch_bounds__(256)
+pil_planes_kernel(const float *__restrict__ src, float *__restrict__ dst, int C, int ih, int iw, int oh, int ow,
+                  const int32_t *__restrict__ xb, const double *__restrict__ xk, int xks, const int32_t *__restrict__ yb,
+                  const double *__restrict__ yk, int yks, const float *__restrict__ factors, int64_t bss, int rows_cap) {
+    extern __shared__ __attribute__((aligned(16))) float s_rows[];          // [rows_cap][kTW]
+    __shared__ double s_xk[kTW * kMaxK], s_yk[kTH * kMaxK];
+    __shared__ int2 s_xb[kTW], s_yb[kTH];
+    const int tid = threadIdx.x;
+    const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+    const int n = blockIdx.z / C, c = blockIdx.z - n * C;
+    const int tw = min(kTW, ow - x0), th = min(kTH, oh - y0);
+
+    if (tid < tw) s_xb[tid] = safe_bounds(xb, x0 + tid, iw, xks);
+    if (tid >= 64 && tid < 64 + th) s_yb[tid - 64] = safe_bounds(yb, y0 + tid - 64, ih, yks);
+    for (int i = tid; i < tw * xks; i += 256) s_xk[i] = xk[(int64_t)x0 * xks + i];
+    for (int i = tid; i < th * yks; i += 256) s_yk[i] = yk[(int64_t)y0 * yks + i];
+    __syncthreads();
+
+    const int r0 = s_yb[0].x;
+    const int rows = min(max(s_yb[th - 1].x + s_yb[th - 1].y - r0, 0), rows_cap);
+    const float *img = src + (int64_t)n * bss + (int64_t)c * ih * iw;
+
+    for (int it = tid; it < rows * kTW; it += 256) {
+        const int r = it >> 6, xl = it & 63;
+        float o = 0.f;
+        if (xl < tw) {
+            const int2 b = s_xb[xl];
+            const float *p = img + (int64_t)(r0 + r) * iw + b.x;
+            const double *k = s_xk + xl * xks;
+            double ss = 0.0;
+            for (int t = 0; t < b.y; ++t) ss += (double)p[t] * k[t];
+            o = (float)ss;
+        }
+        s_rows[it] = o;
+    }
+    __syncthreads();
+
+    const float fac = factors ? factors[c] : 1.0f;
+    float *o = dst + ((int64_t)blockIdx.z * oh + y0) * ow + x0;
+    for (int it = tid; it < th * kTW; it += 256) {
+        const int yl = it >> 6, xl = it & 63;
+        if (xl >= tw) continue;
+        const int2 b = s_yb[yl];
+        const double *k = s_yk + yl * yks;
+        double ss = 0.0;
+        for (int t = 0; t < b.y; ++t) ss += (double)s_rows[min(b.x - r0 + t, rows_cap - 1) * kTW + xl] * k[t];
+        const float v = (float)ss;
+        o[(int64_t)yl * ow + xl] = factors ? v * fac : v;
+    }
+}
+
+// ksize of Pillow's coefficient rows for one axis; 0 when the pair is outside the supported scale range
+int axis_ksize(int in, int out) {
+    if (in <= 0 || out <= 0 || in > kMaxDim || out > kMaxDim) return 0;
+    if ((int64_t)in > (int64_t)kMaxScale * out) return 0;
+    const double scale = (double)in / (double)out;
+    return 2 * (int)ceil(scale < 1.0 ? 1.0 : scale) + 1;
+}
+
+// upper bound of the source samples under `tile` consecutive outputs of one axis: the first tap is >= c0 - support - 0.5, the end of
+// the last <= c1 + support + 0.5 and c1 - c0 = (tile - 1) * scale
+int span_bound(int in, int out, int tile) {
+    const double scale = (double)in / (double)out;
+    const int64_t b = (int64_t)ceil((tile - 1) * scale) + 2 * (int64_t)ceil(scale < 1.0 ? 1.0 : scale) + 2;
+    return (int)(b < in ? b : in);
+}
+static_assert((kTH - 1) * kMaxScale + 2 * kMaxScale + 2 <= kMaxRows, "a tile's staged rows fit the LDS budget at the largest downscale");
+
+constexpr int kRawBudget = 8192;           // bytes of source rows staged at a time
+
+}  // namespace
+
+extern "C" int pwc_pil_resize_ksize(int in_size, int out_size) {
+    const int k = axis_ksize(in_size, out_size);
+    return k ? k : PWC_EINVAL;
+}
+
+extern "C" int pwc_pil_resize_supported(int in_h, int in_w, int out_h, int out_w) {
+    return axis_ksize(in_h, out_h) > 0 && axis_ksize(in_w, out_w) > 0 && (out_h + kTH - 1) / kTH <= 65535;
+}
+
+extern "C" int pwc_pil_resize_frames_u8(const void *frames_u8, void *out_f32, void *out_u8, int n, int H, int W, int h, int w,
+                                        const int32_t *xbounds, const int32_t *xcoef, int xksize, const int32_t *ybounds,
+                                        const int32_t *ycoef, int yksize, const float *lut768, int64_t out_bstride, int out_group,
+                                        void *stream) {
+    if (!frames_u8 || !out_f32 || !xbounds || !xcoef || !ybounds || !ycoef || !lut768)
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: null pointer");
+    if (n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0 || out_group <= 0) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: bad shape");
+    if (!pwc_pil_resize_supported(H, W, h, w))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: %dx%d -> %dx%d is outside the supported scale range (downscale <= 8 per axis)", H, W, h, w);
+    if (xksize != axis_ksize(W, w) || yksize != axis_ksize(H, h))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: ksize (%d, %d) disagrees with the sizes (%d, %d expected)", xksize, yksize,
+                 axis_ksize(W, w), axis_ksize(H, h));
+    const int halves = (n + out_group - 1) / out_group;
+    if (out_bstride < (int64_t)3 * halves * h * w) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: batch stride smaller than the tensor");
+    if (n > 65535) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: grid too large (n > 65535)");
+    if (pwc::misaligned({out_f32, xbounds, xcoef, ybounds, ycoef, lut768}))
+        PWC_FAIL(PWC_EALIGN, "pwc_pil_resize_frames_u8: out / tables must be 4-byte aligned");
+    const int vec = (w % 4 == 0) && pwc::aligned16(out_f32) && (out_bstride % 4 == 0);
+    const int rows_cap = span_bound(H, h, kTH);                              // <= kMaxRows inside the supported range
+    int raw_pitch = (span_bound(W, w, kTW) * 3 + 3 + 3) / 4 * 4;             // a row's bytes + the 3 an unaligned start can add
+    if ((raw_pitch / 4) % 2 == 0) raw_pitch += 4;                           // odd dword pitch: rows start on different banks
+    const int raw_rows = kRawBudget / raw_pitch < 1 ? 1 : (kRawBudget / raw_pitch < rows_cap ? kRawBudget / raw_pitch : rows_cap);
+    const int lds = rows_cap * kPitchB + raw_rows * raw_pitch;               // <= 144 * 196 + 8192 bytes
+    hipLaunchKernelGGL(pil_frames_kernel, dim3((w + kTW - 1) / kTW, (h + kTH - 1) / kTH, n), dim3(256), lds, static_cast<hipStream_t>(stream),
+                       static_cast<const uint8_t *>(frames_u8), static_cast<float *>(out_f32), static_cast<uint8_t *>(out_u8), H, W, h, w,
+                       xbounds, xcoef, xksize, ybounds, ycoef, yksize, lut768, out_bstride, out_group, vec, rows_cap, raw_pitch, raw_rows,
+                       (int64_t)n * H * W * 3);
+    return pwc::check_launch("pil_frames_kernel");
+}
+
+extern "C" int pwc_pil_resize_planes_f32(const void *src, void *dst, int n, int c, int in_h, int in_w, int out_h, int out_w,
+                                         const int32_t *xbounds, const double *xcoef, int xksize, const int32_t *ybounds,
+                                         const double *ycoef, int yksize, const float *factors, int64_t src_bstride, void *stream) {
+    if (!src || !dst || !xbounds || !xcoef || !ybounds || !ycoef) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: null pointer");
+    if (n <= 0 || c <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: bad shape");
+    if (!pwc_pil_resize_supported(in_h, in_w, out_h, out_w))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: %dx%d -> %dx%d is outside the supported scale range (downscale <= 8 per axis)", in_h, in_w,
+                 out_h, out_w);
+    if (xksize != axis_ksize(in_w, out_w) || yksize != axis_ksize(in_h, out_h))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: ksize (%d, %d) disagrees with the sizes (%d, %d expected)", xksize, yksize,
+                 axis_ksize(in_w, out_w), axis_ksize(in_h, out_h));
+    if (src_bstride < (int64_t)c * in_h * in_w) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: batch stride smaller than the tensor");
+    if ((int64_t)n * c > 65535) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: grid too large (n * c > 65535)");
+    if (pwc::misaligned({src, dst, xbounds, ybounds, factors}) || pwc::misaligned({xcoef, ycoef}, 8))
+        PWC_FAIL(PWC_EALIGN, "pwc_pil_resize_planes_f32: planes / bounds must be 4-byte, coefficients 8-byte aligned");
+    const int rows_cap = span_bound(in_h, out_h, kTH);
+    hipLaunchKernelGGL(pil_planes_kernel, dim3((out_w + kTW - 1) / kTW, (out_h + kTH - 1) / kTH, n * c), dim3(256),
+                       rows_cap * kTW * sizeof(float), static_cast<hipStream_t>(stream), static_cast<const float *>(src),
+                       static_cast<float *>(dst), c, in_h, in_w, out_h, out_w, xbounds, xcoef, xksize, ybounds, ycoef, yksize, factors,
+                       src_bstride, rows_cap);
+    return pwc::check_launch("pil_planes_kernel");
+}

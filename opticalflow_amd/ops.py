@@ -495,6 +495,74 @@ def flow_upsample(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, ou
     return out
 
 
+def pil_resize_supported(in_hw, out_hw) -> bool:
+    """True when the Pillow-exact resize kernels take this geometry: scale factors 1/8 .. 8 on both axes (there is no fallback)."""
+    (ih, iw), (oh, ow) = in_hw, out_hw
+    if min(ih, iw, oh, ow) <= 0 or max(ih, iw, oh, ow) >= 2 ** 31:
+        return False
+    return bool(_lib.load().pwc_pil_resize_supported(int(ih), int(iw), int(oh), int(ow)))
+
+
+def _pil_axis_arg(tab, out_size: int, coef_dtype, device, name: str) -> Tuple[int, int, int]:
+    """(bounds, coefficients, ksize) of one axis as pil_resize makes them -> (bounds pointer, coefficient pointer, ksize)."""
+    bounds, coef, ks = tab
+    return (_table_arg(bounds, torch.int32, 2 * out_size, device, name + " bounds"),
+            _table_arg(coef, coef_dtype, ks * out_size, device, name + " coefficients"), int(ks))
+
+
+def pil_resize_frames(frames_u8: torch.Tensor, size: Tuple[int, int], xtab, ytab, lut: torch.Tensor, out: torch.Tensor,
+                      out_u8: Optional[torch.Tensor] = None, group: Optional[int] = None) -> torch.Tensor:
+    """uint8 RGB frames [n,H,W,3] -> out float32 [group, 3*ceil(n/group), h, w] (dense planes, free batch stride): Pillow's BILINEAR
+    resize in its 8-bit fixed point, then lut[c][byte] (C-ABI pwc_pil_resize_frames_u8).  xtab / ytab: (bounds int32 [O,2],
+    coefficients int32 [O,ksize], ksize) on the device; lut float32 [3,256]; out_u8: optional resized bytes [n,h,w,3]."""
+    _require_device(frames_u8, "frames_u8")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise ValueError("frames_u8 must be a contiguous uint8 device tensor [n,H,W,3]")
+    n, H, W, _ = frames_u8.shape
+    h, w = size
+    group = n if group is None else int(group)
+    dev = frames_u8.device
+    if group <= 0:
+        raise ValueError("group must be positive")
+    want = (min(group, n), 3 * ((n + group - 1) // group), h, w)
+    if out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != want:
+        raise ValueError("out must be float32 %s on %s, got %s %s on %s" % (want, dev, out.dtype, tuple(out.shape), out.device))
+    bso = _plane_dense(out, "out")
+    if out_u8 is not None and (out_u8.dtype != torch.uint8 or tuple(out_u8.shape) != (n, h, w, 3) or out_u8.device != dev
+                               or not out_u8.is_contiguous()):
+        raise ValueError("out_u8 must be a contiguous uint8 %s tensor on %s" % ((n, h, w, 3), dev))
+    xb, xk, xks = _pil_axis_arg(xtab, w, torch.int32, dev, "x")
+    yb, yk, yks = _pil_axis_arg(ytab, h, torch.int32, dev, "y")
+    lp = _table_arg(lut, torch.float32, 768, dev, "lut")
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_pil_resize_frames_u8(frames_u8.data_ptr(), out.data_ptr(), _ptr(out_u8), n, H, W, h, w, xb, xk, xks,
+                                                  yb, yk, yks, lp, bso, group, _stream(frames_u8))
+    check(rc, "pwc_pil_resize_frames_u8")
+    return out
+
+
+def pil_resize_planes(x: torch.Tensor, size: Tuple[int, int], xtab, ytab, factors: Optional[torch.Tensor] = None,
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 planes [n,c,h,w] (dense planes, free batch stride) -> [n,c,H,W] as Pillow resizes mode "F" images (double accumulation
+    in tap order, float32 between the passes), times factors[c] (float32 [c] on the device) when given (C-ABI
+    pwc_pil_resize_planes_f32).  xtab / ytab: (bounds int32 [O,2], coefficients float64 [O,ksize], ksize) on the device."""
+    if x.dtype != torch.float32:
+        raise ValueError("x must be float32, got %s" % x.dtype)
+    x = densify(x)
+    bsx = _plane_dense(x, "x")
+    n, c, h, w = x.shape
+    H, W = size
+    out = _out_arg(out, (n, c, H, W), torch.float32, x.device, contiguous=True)
+    xb, xk, xks = _pil_axis_arg(xtab, W, torch.float64, x.device, "x")
+    yb, yk, yks = _pil_axis_arg(ytab, H, torch.float64, x.device, "y")
+    fp = None if factors is None else _table_arg(factors, torch.float32, c, x.device, "factors")
+    with torch.cuda.device(x.device):
+        rc = _lib.load().pwc_pil_resize_planes_f32(x.data_ptr(), out.data_ptr(), n, c, h, w, H, W, xb, xk, xks, yb, yk, yks, fp, bsx,
+                                                   _stream(x))
+    check(rc, "pwc_pil_resize_planes_f32")
+    return out
+
+
 def kitti_score_workspace_bytes(n: int, out_h: int, out_w: int) -> int:
     return _query_bytes(_lib.load().pwc_kitti_score_workspace_bytes(n, out_h, out_w), "kitti-score")
 

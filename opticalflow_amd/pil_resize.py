@@ -1,0 +1,254 @@
+"""Pillow-exact bilinear resize on the device: the host-only first stage of train_pseudo.py / train_fundamental.py / inference.py
+(transforms.Resize -> ToTensor -> Normalize on 8-bit frames) and inference.py's resize_flow (Pillow on float planes), bit for bit.
+
+The coefficient tables are made here on the host (`coeff_tables`, `fixed_point`: Python floats are C doubles and int() truncates like
+the C cast, so they are Pillow's), uploaded once per (input length, output length, device) and kept; the kernels of
+csrc/pwc_pil_resize.hip only apply them.  Once the tables of a geometry are resident, `resize_frames` / `resize_flow` neither
+allocate tables nor synchronise and can be captured in a HIP graph.  There is no CPU fallback: outside the supported scale range
+(ops.pil_resize_supported) the calls raise."""
+from __future__ import annotations
+
+import math
+from typing import Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+PRECISION_BITS = 22          # 32 - 8 - 2: Pillow's fixed point for 8-bit images
+IMAGENET_MEAN = (0.485, 0.456, 0.406)
+IMAGENET_STD = (0.229, 0.224, 0.225)
+
+
+# ------------------------------------------------------------------ host tables (no GPU needed)
+def ksize(in_size: int, out_size: int) -> int:
+    """Length of one coefficient row: 2 * ceil(support) + 1 with support = max(in / out, 1)."""
+    return 2 * int(math.ceil(max(in_size / out_size, 1.0))) + 1
+
+
+def coeff_tables(in_size: int, out_size: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's BILINEAR coefficients of one axis: bounds int32 [out, 2] = (first tap, number of taps) and float64 [out, ksize]
+    weights, normalised by their sum in tap order, zero past the last tap."""
+    if in_size <= 0 or out_size <= 0:
+        raise ValueError("sizes must be positive, got %d -> %d" % (in_size, out_size))
+    scale = in_size / out_size
+    fs = max(scale, 1.0)
+    support = 1.0 * fs
+    ks = ksize(in_size, out_size)
+    inv = 1.0 / fs
+    bounds = np.zeros((out_size, 2), np.int32)
+    coeffs = np.zeros((out_size, ks), np.float64)
+    for xx in range(out_size):
+        center = (xx + 0.5) * scale
+        xmin = max(int(center - support + 0.5), 0)
+        xmax = min(int(center + support + 0.5), in_size) - xmin
+        ww = 0.0
+        row = []
+        for x in range(xmax):
+            t = (x + xmin - center + 0.5) * inv
+            if t < 0.0:
+                t = -t
+            w = 1.0 - t if t < 1.0 else 0.0
+            row.append(w)
+            ww += w
+        if ww != 0.0:
+            row = [w / ww for w in row]
+        bounds[xx] = (xmin, xmax)
+        coeffs[xx, :xmax] = row
+    return bounds, coeffs
+
+
+def fixed_point(coeffs: np.ndarray) -> np.ndarray:
+    """The 8-bit path's int32 coefficients: (int)(w * 2^22 + 0.5), or - 0.5 for a negative one (truncation toward zero)."""
+    c = np.asarray(coeffs, np.float64)
+    return np.trunc(c * float(1 << PRECISION_BITS) + np.where(c < 0.0, -0.5, 0.5)).astype(np.int32)
+
+
+def norm_lut(mean: Optional[Sequence[float]] = None, std: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """float32 [3, 256] on the host: ToTensor (float(u8) / 255) and, with mean / std, Normalize ((v - mean[c]) / std[c]) of every byte
+    value, made with torch's own CPU operators so that indexing it equals running them."""
+    if (mean is None) != (std is None):
+        raise ValueError("mean and std go together")
+    v = torch.arange(256, dtype=torch.uint8).to(torch.float32).div(255)
+    if mean is None:
+        return v.expand(3, 256).contiguous()
+    m = torch.as_tensor([float(x) for x in mean], dtype=torch.float32)
+    s = torch.as_tensor([float(x) for x in std], dtype=torch.float32)
+    if m.numel() != 3 or s.numel() != 3 or bool((s == 0).any()):
+        raise ValueError("mean / std must have three entries and std no zero")
+    return v.expand(3, 256).clone().sub_(m[:, None]).div_(s[:, None])
+
+
+# ------------------------------------------------------------------ resident device tables
+_TABLES = {}
+_LUTS = {}
+_FACTORS = {}
+
+
+def _axis_tables(in_size: int, out_size: int, fixed: bool, device):
+    key = (in_size, out_size, fixed, str(device))
+    got = _TABLES.get(key)
+    if got is None:
+        b, c = coeff_tables(in_size, out_size)
+        k = fixed_point(c) if fixed else c
+        got = (torch.from_numpy(b).to(device), torch.from_numpy(k).to(device), c.shape[1])
+        _TABLES[key] = got
+    return got
+
+
+def _lut(mean, std, device) -> torch.Tensor:
+    key = (None if mean is None else tuple(float(x) for x in mean), None if std is None else tuple(float(x) for x in std), str(device))
+    got = _LUTS.get(key)
+    if got is None:
+        got = _LUTS[key] = norm_lut(mean, std).to(device)
+    return got
+
+
+def _size(size) -> Tuple[int, int]:
+    h, w = (int(v) for v in size)
+    return h, w
+
+
+def _check_supported(in_hw, out_hw) -> None:
+    from . import ops
+    if not ops.pil_resize_supported(in_hw, out_hw):
+        raise ValueError("resize %dx%d -> %dx%d is outside the supported range (a downscale of at most 8 per axis); there is no "
+                         "fallback" % (in_hw[0], in_hw[1], out_hw[0], out_hw[1]))
+
+
+def prepare(in_hw, out_hw, device, frames: bool = True, mean=None, std=None) -> None:
+    """Make the tables of one geometry resident (what the first call does), e.g. before capturing a graph."""
+    _check_supported(in_hw, out_hw)
+    _axis_tables(in_hw[1], out_hw[1], frames, device)
+    _axis_tables(in_hw[0], out_hw[0], frames, device)
+    if frames:
+        _lut(mean, std, device)
+
+
+# ------------------------------------------------------------------ operators
+def _resize_frames(frames_u8: torch.Tensor, size, mean, std, out: torch.Tensor, out_u8: Optional[torch.Tensor], group: int):
+    from . import ops
+    n, H, W, _ = frames_u8.shape
+    h, w = size
+    _check_supported((H, W), (h, w))
+    xt = _axis_tables(W, w, True, frames_u8.device)
+    yt = _axis_tables(H, h, True, frames_u8.device)
+    return ops.pil_resize_frames(frames_u8, (h, w), xt, yt, _lut(mean, std, frames_u8.device), out, out_u8, group)
+
+
+def resize_frames(frames_u8: torch.Tensor, size, mean=None, std=None, out: Optional[torch.Tensor] = None, return_u8: bool = False):
+    """uint8 RGB frames [n,H,W,3] on the device -> float32 [n,3,h,w]: Image.resize((w, h), BILINEAR) + ToTensor, and with mean / std
+    Normalize, as one kernel.  `out` may be a channel slice of a larger tensor (e.g. x[:, 3:6]).  return_u8: also the resized bytes
+    [n,h,w,3] (what Pillow returns), as a second result."""
+    if frames_u8.dim() != 4 or frames_u8.shape[3] != 3 or frames_u8.dtype != torch.uint8:
+        raise ValueError("frames_u8 must be uint8 [n,H,W,3], got %s %s" % (frames_u8.dtype, tuple(frames_u8.shape)))
+    h, w = _size(size)
+    n = frames_u8.shape[0]
+    if out is None:
+        out = torch.empty((n, 3, h, w), dtype=torch.float32, device=frames_u8.device)
+    u8 = torch.empty((n, h, w, 3), dtype=torch.uint8, device=frames_u8.device) if return_u8 else None
+    _resize_frames(frames_u8, (h, w), mean, std, out, u8, n)
+    return (out, u8) if return_u8 else out
+
+
+def resize_planes(x: torch.Tensor, size, factors: Optional[Sequence[float]] = None) -> torch.Tensor:
+    """float32 planes [n,c,h,w] on the device -> [n,c,H,W] as Pillow resizes mode "F" images; factors: one float per channel,
+    multiplied in float32 after the resize."""
+    from . import ops
+    if x.dim() != 4 or x.dtype != torch.float32:
+        raise ValueError("x must be float32 [n,c,h,w], got %s %s" % (x.dtype, tuple(x.shape)))
+    H, W = _size(size)
+    n, c, h, w = x.shape
+    _check_supported((h, w), (H, W))
+    xt = _axis_tables(w, W, False, x.device)
+    yt = _axis_tables(h, H, False, x.device)
+    fac = None
+    if factors is not None:
+        key = (tuple(float(np.float32(f)) for f in factors), str(x.device))
+        if len(key[0]) != c:
+            raise ValueError("factors must have one entry per channel (%d), got %d" % (c, len(key[0])))
+        fac = _FACTORS.get(key)
+        if fac is None:
+            fac = _FACTORS[key] = torch.tensor(key[0], dtype=torch.float32).to(x.device)
+    return ops.pil_resize_planes(x, (H, W), xt, yt, fac)
+
+
+def resize_flow(flow: torch.Tensor, size, scale_vectors: bool = True) -> torch.Tensor:
+    """inference.py's resize_flow for a batch: [B,2,h,w] -> [B,2,H,W] with Pillow's BILINEAR on float planes, then u * (W / w) and
+    v * (H / h) (the factor rounded to float32, the product in float32)."""
+    if flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError("flow must be [B,2,h,w], got %s" % (tuple(flow.shape),))
+    H, W = _size(size)
+    h, w = flow.shape[2:]
+    return resize_planes(flow, (H, W), (W / w, H / h) if scale_vectors else None)
+
+
+class FrameIngest:
+    """Batches of raw uint8 frame pairs -> the normalised [B,6,h,w] network input: the frames of a batch go through a pinned host slot
+    in ONE upload and ONE resize call.  Two slots alternate, so filling the next batch does not wait for the previous upload."""
+
+    def __init__(self, size, mean=IMAGENET_MEAN, std=IMAGENET_STD, device="cuda", batch: int = 4):
+        self.size = _size(size)
+        self.mean, self.std = mean, std
+        self.device = torch.device(device)
+        self.batch = int(batch)
+        if self.batch <= 0:
+            raise ValueError("batch must be positive")
+        self._slots = [None, None]
+        self._events = [None, None]
+        self._turn = 0
+        self._dev = None
+
+    def _slot(self, H: int, W: int) -> Tuple[torch.Tensor, int]:
+        i = self._turn
+        self._turn ^= 1
+        shape = (2 * self.batch, H, W, 3)
+        if self._slots[i] is None or tuple(self._slots[i].shape) != shape:
+            self._slots[i] = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
+        elif self._events[i] is not None:
+            self._events[i].synchronize()          # the upload that last read this slot has finished
+        return self._slots[i], i
+
+    def pairs(self, frames1, frames2, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """frames1 / frames2: B host frames each ([B,H,W,3] uint8 tensor / array, or a sequence of [H,W,3]), all of one size ->
+        (img1, img2), the channel halves [:, :3] and [:, 3:] of one [B,6,h,w] tensor (`img1._base`)."""
+        fr = [torch.as_tensor(np.asarray(f)) if not torch.is_tensor(f) else f for f in list(frames1) + list(frames2)]
+        B = len(fr) // 2
+        if B == 0 or len(fr) != 2 * B or len(frames1) != B or B > self.batch:
+            raise ValueError("pairs() takes 1..%d frames per side, the same number on both" % self.batch)
+        H, W = fr[0].shape[:2]
+        for f in fr:
+            if f.dtype != torch.uint8 or tuple(f.shape) != (H, W, 3):
+                raise ValueError("all frames of one call must be uint8 [%d,%d,3]; got %s %s" % (H, W, f.dtype, tuple(f.shape)))
+        _check_supported((H, W), self.size)
+        slot, i = self._slot(H, W)
+        for j, f in enumerate(fr):
+            slot[j].copy_(f)
+        if self._dev is None or tuple(self._dev.shape) != tuple(slot.shape):
+            self._dev = torch.empty(slot.shape, dtype=torch.uint8, device=self.device)
+        dev = self._dev[:2 * B]
+        dev.copy_(slot[:2 * B], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        self._events[i] = ev
+        h, w = self.size
+        if out is None:
+            out = torch.empty((B, 6, h, w), dtype=torch.float32, device=self.device)
+        _resize_frames(dev, self.size, self.mean, self.std, out, None, B)
+        return out[:, :3], out[:, 3:]
+
+
+@torch.no_grad()
+def infer_resized(model, frames1_u8: torch.Tensor, frames2_u8: torch.Tensor, image_size, mean=IMAGENET_MEAN, std=IMAGENET_STD):
+    """The loop body of inference.py:217-236 on the device: both frames [B,H,W,3] uint8 resized to image_size and normalised into
+    one [B,6,h,w] input, the forward pass, and the flow resized back to (H, W) with its vectors rescaled -> [B,2,H,W]."""
+    if frames1_u8.shape != frames2_u8.shape:
+        raise ValueError("the two frame batches must have one shape")
+    B, H, W, _ = frames1_u8.shape
+    h, w = _size(image_size)
+    x = torch.empty((B, 6, h, w), dtype=torch.float32, device=frames1_u8.device)
+    resize_frames(frames1_u8, (h, w), mean, std, out=x[:, :3])
+    resize_frames(frames2_u8, (h, w), mean, std, out=x[:, 3:])
+    flow = model(x)
+    if isinstance(flow, (list, tuple)):
+        flow = flow[0]
+    return resize_flow(flow, (H, W))
