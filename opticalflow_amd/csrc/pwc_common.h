@@ -63,6 +63,20 @@ __device__ __forceinline__ float mask_val(const void *mask, int mask_u8, int64_t
     return static_cast<const float *>(mask)[off];
 }
 
+// What the caller of a Winograd entry (pwc_conv3x3_wino_fwd, pwc_conv3x3_wino4_fwd) passed, checked and cast: the same for every launch
+// of the layer.  `dil` is 1 and `split2` 0 where the family has no such form.
+struct WinoArgs {
+    const float *x, *up, *bias;
+    float *y;
+    int B, Cin, H, W, Cout, dil;
+    int64_t bsx, bsy;
+    float slope;
+    int do_leaky, split2;
+    void *ws;
+    int64_t ws_bytes;
+    hipStream_t st;
+};
+
 // Raise a kernel's dynamic-LDS limit once per (kernel instantiation, device).  `done` is a per-instantiation
 // static array; relaxed atomics are enough (setting the attribute twice is harmless).
 constexpr int kMaxDevices = 64;

@@ -388,46 +388,55 @@ conv3x3_wino8r_kernel(const float *__restrict__ x, const float *__restrict__ up,
 
 inline int cout_padded(int Cout) { return (Cout + 31) / 32 * 32; }
 
-template <int MT>
-int launch_wino(const float *x, const float *up, const float *bias, float *y, int B, int Cin, int H, int W, int Cout, int dil,
-                int64_t bsx, int64_t bsy, float slope, int do_leaky, hipStream_t st, int co0, int ngroups,
-                int ksplit = 1, int cps = 0, float *part = nullptr) {
-    using G = Geo<MT>;
-    const int CoutP = cout_padded(Cout);
-    const int Hs = (H + dil - 1) / dil, Ws = (W + dil - 1) / dil;            // the largest of the D*D lattices
-    const int tiles_x = (Ws + kTW - 1) / kTW, tiles_y = (Hs + kGH * G::kTG - 1) / (kGH * G::kTG);
-    const int64_t nblk = (int64_t)B * tiles_x * tiles_y * dil * dil;
-    if (nblk > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino_fwd: grid too large");
-    int vec2 = dil == 1 && (W % 2 == 0) && (bsy % 2 == 0) && !(reinterpret_cast<uintptr_t>(y) & 7u);
-    if (vec2 && (W % 4 == 0) && (bsy % 4 == 0) && !(reinterpret_cast<uintptr_t>(y) & 15u)) vec2 = 2;      // 16-byte stores (8-wave kernel)
-    static pwc::LdsAttrOnce once8r;
-    if (const int rc = pwc::ensure_lds_attr(once8r, reinterpret_cast<const void *>(&conv3x3_wino8r_kernel<MT>), GeoR<MT>::kSmemBytes,
-                                            "conv3x3_wino8r_kernel"))
-        return rc;
-    hipLaunchKernelGGL(conv3x3_wino8r_kernel<MT>, dim3((unsigned)nblk, (unsigned)ngroups, (unsigned)ksplit), dim3(kThreads8),
-                       GeoR<MT>::kSmemBytes, st, x, up, bias, y, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky,
-                       vec2, dil, co0, cps, part, (int64_t)B * Cout * H * W);
-    pwc::note_kernel("conv3x3_wino8r_kernel", MT, G::kTG, 1, dil, 1, 0);
-    return pwc::check_launch("conv3x3_wino8r_kernel");
-}
-
-// Launch shape of a layer run with ONE cout-tile width (the widest that divides CoutP), and its split-K plan: a launch that leaves
-// most CUs idle (levels 5-4: 64-128 workgroups) is cut along Cin into ksplit slices of cps chunks (>= 8 chunks each: a tile costs
-// ~9 us outside its K loop), partial sums go to the caller's workspace, pwc_conv::splitk_reduce adds them in fixed order.
-struct WinoPlan { int mt, ksplit, cps; int64_t nwg; double fill; };
+// ---- the layer plan ---------------------------------------------------------------------------------------------------------------------
+// THE description of how a layer becomes launches: the rule (pwc_conv3x3_wino_preferred), the scratch query
+// (pwc_conv3x3_wino_workspace_bytes) and pwc_conv3x3_wino_fwd all read it.
+// A launch runs ngroups cout tiles of 32 mt couts from co0 on nblk workgroups each (one per 4 (4 / mt) rows x 32 columns of one of the D*D
+// pixel lattices of ceil(H / D) x ceil(W / D) of an image).
+struct WinoLaunch { int mt, co0, ngroups, tiles_x, tiles_y; int64_t nblk; };
+// `one`: the layer as ONE launch of the widest cout tile that divides CoutP -- what the rule is measured against (nwg workgroups, the
+// share `fill` of their tiles inside the lattice) and the launch of the split-K form: one that leaves most CUs idle (levels 5-4: 64-128
+// workgroups) is cut along Cin into ksplit slices of cps chunks (>= 8 chunks each: a tile costs ~9 us outside its K loop), partial sums
+// go to the caller's workspace (ws_bytes), pwc_conv::splitk_reduce adds them in fixed order.
+// `l[0 .. n)`: the launches of the layer run unsplit -- cout blocks of 32: as many 128-wide workgroups as fit, then a 64-wide and a 32-wide
+// launch for the rest (96 = 64 + 32: the wider the cout tile, the fewer tile groups share a workgroup and the smaller the transform's share
+// of the issue slots) when the narrowest of them still covers the chip; otherwise `one`.
+struct WinoPlan {
+    int mt, ksplit, cps;
+    int64_t nwg, ws_bytes;
+    double fill;
+    WinoLaunch one;
+    int n;
+    WinoLaunch l[3];
+};
 WinoPlan wino_plan(int B, int Cin, int H, int W, int Cout, int dilation) {
-    const int CoutP = cout_padded(Cout);
+    const int CoutP = cout_padded(Cout), nblk32 = CoutP / 32;
     const int mt = (CoutP % 128 == 0) ? 4 : (CoutP % 64 == 0) ? 2 : 1;
     const int gh = kGH * (4 / mt);
-    const int Hs = (H + dilation - 1) / dilation, Ws = (W + dilation - 1) / dilation;
-    const int tiles_x = (Ws + kTW - 1) / kTW, tiles_y = (Hs + gh - 1) / gh;
-    WinoPlan p;
+    const int Hs = (H + dilation - 1) / dilation, Ws = (W + dilation - 1) / dilation;            // the largest of the D*D lattices
+    auto launch = [&](int lmt, int co0, int ngroups) {
+        const int tiles_x = (Ws + kTW - 1) / kTW, tiles_y = (Hs + kGH * (4 / lmt) - 1) / (kGH * (4 / lmt));
+        return WinoLaunch{lmt, co0, ngroups, tiles_x, tiles_y, (int64_t)B * tiles_x * tiles_y * dilation * dilation};
+    };
+    WinoPlan p{};
     p.mt = mt;
-    p.nwg = (int64_t)B * tiles_x * tiles_y * dilation * dilation * (CoutP / (32 * mt));
-    p.fill = (double)Hs * Ws / ((double)tiles_y * gh * tiles_x * kTW);
+    p.one = launch(mt, 0, nblk32 / mt);
+    p.nwg = p.one.nblk * p.one.ngroups;
+    p.fill = (double)Hs * Ws / ((double)p.one.tiles_y * gh * p.one.tiles_x * kTW);
+    static const int force_mt = [] { const char *e = getenv("PWC_WINO_MT"); return (e && *e) ? atoi(e) : 0; }();    // experiments
+    const bool ragged = (nblk32 % 4) != 0 && nblk32 != 1 && nblk32 != 2;
+    if (force_mt == 1 || force_mt == 2) {
+        p.l[p.n++] = (force_mt == 2 && nblk32 % 2 == 0) ? launch(2, 0, nblk32 / 2) : launch(1, 0, nblk32);
+    } else if (ragged && launch(nblk32 % 2 ? 1 : 2, 0, 1).nblk < 256) {
+        p.l[p.n++] = p.one;
+    } else {
+        int co0 = 0;
+        if (nblk32 >= 4) { p.l[p.n++] = launch(4, 0, nblk32 / 4); co0 = nblk32 / 4 * 128; }
+        if ((nblk32 % 4) >= 2) { p.l[p.n++] = launch(2, co0, 1); co0 += 64; }
+        if (nblk32 % 2) p.l[p.n++] = launch(1, co0, 1);
+    }
     const int nchunks = (Cin + kCK - 1) / kCK;
     p.ksplit = 1;
-    p.cps = 0;
     static const int knob = [] { const char *e = getenv("PWC_WINO_SPLIT"); return (e && *e) ? atoi(e) : -1; }();
     // measured (tools/bench_wino.py layers): with 64 workgroups (level 5 at batch 16) the split form only ties the direct kernel's own
     // split-K; from ~100 (conv4_3: 128) it wins 1.35x
@@ -439,9 +448,31 @@ WinoPlan wino_plan(int B, int Cin, int H, int W, int Cout, int dilation) {
         if (ks >= 2) {
             p.cps = (nchunks + ks - 1) / ks;
             p.ksplit = (nchunks + p.cps - 1) / p.cps;
+            p.ws_bytes = (int64_t)p.ksplit * B * Cout * H * W * (int64_t)sizeof(float);
         }
     }
     return p;
+}
+
+// One launch record of the plan; ksplit > 1: its split-K form, partial sums to `part`
+template <int MT>
+int launch_wino(const WinoLaunch &l, const pwc::WinoArgs &a, int ksplit, int cps, float *part) {
+    using G = Geo<MT>;
+    if (l.nblk > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino_fwd: grid too large");
+    int vec2 = a.dil == 1 && (a.W % 2 == 0) && (a.bsy % 2 == 0) && !(reinterpret_cast<uintptr_t>(a.y) & 7u);
+    if (vec2 && (a.W % 4 == 0) && (a.bsy % 4 == 0) && !(reinterpret_cast<uintptr_t>(a.y) & 15u)) vec2 = 2;      // 16-byte stores (8-wave kernel)
+    static pwc::LdsAttrOnce once8r;
+    if (const int rc = pwc::ensure_lds_attr(once8r, reinterpret_cast<const void *>(&conv3x3_wino8r_kernel<MT>), GeoR<MT>::kSmemBytes,
+                                            "conv3x3_wino8r_kernel"))
+        return rc;
+    hipLaunchKernelGGL(conv3x3_wino8r_kernel<MT>, dim3((unsigned)l.nblk, (unsigned)l.ngroups, (unsigned)ksplit), dim3(kThreads8),
+                       GeoR<MT>::kSmemBytes, a.st, a.x, a.up, a.bias, a.y, a.Cin, a.H, a.W, a.Cout, cout_padded(a.Cout), l.tiles_x, l.tiles_y, a.bsx, a.bsy,
+                       a.slope, a.do_leaky, vec2, a.dil, l.co0, cps, part, (int64_t)a.B * a.Cout * a.H * a.W);
+    pwc::note_kernel("conv3x3_wino8r_kernel", MT, G::kTG, 1, a.dil, 1, 0);
+    return pwc::check_launch("conv3x3_wino8r_kernel");
+}
+inline int launch_wino(const WinoLaunch &l, const pwc::WinoArgs &a, int ksplit = 1, int cps = 0, float *part = nullptr) {
+    return l.mt == 4 ? launch_wino<4>(l, a, ksplit, cps, part) : l.mt == 2 ? launch_wino<2>(l, a, ksplit, cps, part) : launch_wino<1>(l, a, ksplit, cps, part);
 }
 
 }  // namespace
@@ -458,8 +489,7 @@ extern "C" int pwc_conv3x3_wino_preferred(int B, int Cin, int H, int W, int Cout
 /* bytes of workspace the split-K form of this layer wants (0: it does not split) */
 extern "C" int64_t pwc_conv3x3_wino_workspace_bytes(int B, int Cin, int H, int W, int Cout, int dilation) {
     if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || dilation < 1) return -1;
-    const WinoPlan p = wino_plan(B, Cin, H, W, Cout, dilation);
-    return p.ksplit > 1 ? (int64_t)p.ksplit * B * Cout * H * W * (int64_t)sizeof(float) : 0;
+    return wino_plan(B, Cin, H, W, Cout, dilation).ws_bytes;
 }
 
 extern "C" int64_t pwc_conv3x3_wino_packed_bytes(int Cin, int Cout) {
@@ -489,52 +519,17 @@ extern "C" int pwc_conv3x3_wino_fwd(const void *x, const void *up, const void *b
     const int64_t plane = (int64_t)H * W;
     if (x_bstride < Cin * plane || y_bstride < Cout * plane) PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino_fwd: batch stride smaller than the tensor");
     if (plane * kCK * 4 >= 0x7fffffffLL) PWC_FAIL(PWC_EUNSUPPORTED, "pwc_conv3x3_wino_fwd: image plane too large for 32-bit DMA offsets");
-    const float *xf = static_cast<const float *>(x), *uf = static_cast<const float *>(up), *bf = static_cast<const float *>(bias);
-    float *yf = static_cast<float *>(y);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int do_leaky = (flags & PWC_ACT_LEAKY) ? 1 : 0;
-    const int CoutP = cout_padded(Cout);
-    // cout blocks of 32: as many 128-wide workgroups as fit, then a 64-wide and a 32-wide launch for the rest (96 = 64 + 32: the
-    // wider the cout tile, the fewer tile groups share a workgroup and the smaller the transform's share of the issue slots)
-    static const int force_mt = [] { const char *e = getenv("PWC_WINO_MT"); return (e && *e) ? atoi(e) : 0; }();    // experiments
-    const int nblk32 = CoutP / 32;
+    const pwc::WinoArgs a{static_cast<const float *>(x), static_cast<const float *>(up), static_cast<const float *>(bias), static_cast<float *>(y),
+                          B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, (flags & PWC_ACT_LEAKY) ? 1 : 0, 0,
+                          workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const WinoPlan p = wino_plan(B, Cin, H, W, Cout, dilation);
     // split-K for launches that would leave most CUs idle (needs the caller's workspace; without it the layer runs unsplit)
-    const WinoPlan sp = wino_plan(B, Cin, H, W, Cout, dilation);
-    if (sp.ksplit > 1 && workspace && !(reinterpret_cast<uintptr_t>(workspace) & 3u) &&
-        workspace_bytes >= (int64_t)sp.ksplit * B * Cout * plane * (int64_t)sizeof(float)) {
+    if (p.ksplit > 1 && workspace && !(reinterpret_cast<uintptr_t>(workspace) & 3u) && workspace_bytes >= p.ws_bytes) {
         float *part = static_cast<float *>(workspace);
-        int rc;
-        if (sp.mt == 4) rc = launch_wino<4>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32 / 4, sp.ksplit, sp.cps, part);
-        else if (sp.mt == 2) rc = launch_wino<2>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32 / 2, sp.ksplit, sp.cps, part);
-        else rc = launch_wino<1>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32, sp.ksplit, sp.cps, part);
-        if (rc) return rc;
-        return pwc_conv::splitk_reduce(part, bf, nullptr, yf, B, Cout, (int)plane, sp.ksplit, y_bstride, 0, leaky_slope, do_leaky, st);
+        if (const int rc = launch_wino(p.one, a, p.ksplit, p.cps, part)) return rc;
+        return pwc_conv::splitk_reduce(part, a.bias, nullptr, a.y, B, Cout, (int)plane, p.ksplit, y_bstride, 0, leaky_slope, a.do_leaky, a.st);
     }
-    int co0 = 0;
-    if (force_mt == 1 || force_mt == 2) {
-        if (force_mt == 2 && nblk32 % 2 == 0)
-            return launch_wino<2>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32 / 2);
-        return launch_wino<1>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32);
-    }
-    // ... when the narrowest launch still covers the chip; otherwise one launch of the widest tile that divides CoutP
-    const int Hs = (H + dilation - 1) / dilation, Ws = (W + dilation - 1) / dilation;
-    const int64_t wg32 = (int64_t)B * ((Ws + kTW - 1) / kTW) * ((Hs + 4 * kGH - 1) / (4 * kGH)) * dilation * dilation;   // 32-cout launch
-    const int64_t wg64 = (int64_t)B * ((Ws + kTW - 1) / kTW) * ((Hs + 2 * kGH - 1) / (2 * kGH)) * dilation * dilation;
-    const bool ragged = (nblk32 % 4) != 0 && nblk32 != 1 && nblk32 != 2;
-    if (ragged && ((nblk32 % 2) ? wg32 : wg64) < 256) {
-        if (nblk32 % 2 == 0)
-            return launch_wino<2>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32 / 2);
-        return launch_wino<1>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32);
-    }
-    if (nblk32 >= 4) {
-        if (const int rc = launch_wino<4>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, 0, nblk32 / 4)) return rc;
-        co0 = nblk32 / 4 * 128;
-    }
-    if ((nblk32 % 4) >= 2) {
-        if (const int rc = launch_wino<2>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, co0, 1)) return rc;
-        co0 += 64;
-    }
-    if (nblk32 % 2)
-        return launch_wino<1>(xf, uf, bf, yf, B, Cin, H, W, Cout, dilation, x_bstride, y_bstride, leaky_slope, do_leaky, st, co0, 1);
+    for (int i = 0; i < p.n; ++i)
+        if (const int rc = launch_wino(p.l[i], a)) return rc;
     return PWC_OK;
 }

@@ -713,55 +713,6 @@ inline TailPlan wino4_tail_plan(int B, int64_t nblk, int ngroups, int nchunks, i
     return p;
 }
 
-// The staggered schedule pays in the K loop and costs at its ends (four specialisations of the unrolled body instead of two are
-// fetched): x1.02-1.04 from 24 chunks per workgroup up, x1.00 at 16, x0.96-0.98 at the 8-11 chunks of a slice of a small launch
-constexpr int kStaggerMinChunks = 16;
-
-template <int CB, int TG, int GW, int IH = 0>
-int launch_wino4(const float *x, const float *up, const float *bias, float *y, int B, int Cin, int H, int W, int Cout,
-                 int64_t bsx, int64_t bsy, float slope, int do_leaky, hipStream_t st, int co0, int ngroups, int split2,
-                 void *workspace, int64_t workspace_bytes) {
-    using G = Geo4<CB, TG, GW, IH>;
-    constexpr int kSmemP = G::kSmemBytes > 8 * 64 * 64 * 4 ? G::kSmemBytes : 8 * 64 * 64 * 4;       // rings, or the 128 KiB of the final exchange
-    static pwc::LdsAttrOnce once;
-    if (const int rc = pwc::ensure_lds_attr(once, reinterpret_cast<const void *>(&conv3x3_wino4p_kernel<CB, TG, GW, IH>), kSmemP, "conv3x3_wino4p_kernel"))
-        return rc;
-    if (IH && (H > IH || W > GW || Cin % kCK || (int64_t)(G::kImg - 1) * bsx * 4 + (int64_t)kCK * H * W * 4 > 0x7fffffffLL))
-        PWC_FAIL(PWC_EUNSUPPORTED, "pwc_conv3x3_wino4_fwd: stacked tile groups need H <= %d, W <= %d, Cin %% 4 == 0 and 31-bit offsets", IH, GW);
-    const int CoutP = cout_padded4(Cout);
-    constexpr int kTH = G::kTH;
-    // option "w4_stagger": 0 = every wave on the parent schedule, 1 = waves 4-7 staggered in the forms where that measured faster
-    // (Geo4::kStagger) and for workgroups of at least kStaggerMinChunks chunks, 2 = in every launch (measurements)
-    const int sopt = pwc::option(pwc::OPT_W4_STAGGER);
-    auto stagger_for = [&](int chunks) { return (sopt >= 2 || (sopt == 1 && G::kStagger && chunks >= kStaggerMinChunks)) ? 1 : 0; };
-    // stacked: the tile arithmetic (tail split, XCD order) runs over groups of kImg images, as the plain form runs over images
-    const int Bg = (B + G::kImg - 1) / G::kImg;
-    const int tiles_x = (W + GW - 1) / GW, tiles_y = IH ? 1 : (H + kTH - 1) / kTH;
-    const int64_t nblk = (int64_t)Bg * tiles_x * tiles_y;
-    if (nblk * ngroups > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino4_fwd: grid too large");
-    TailPlan tp = wino4_tail_plan(Bg, nblk, ngroups, (Cin + kCK - 1) / kCK, Cout, kTH * GW, split2);
-    if (tp.ksplit > 1 && (!workspace || workspace_bytes < tp.ws_bytes || (reinterpret_cast<uintptr_t>(workspace) & 15u))) tp = TailPlan{(int)nblk, 1, 0, 0};
-    if (tp.main_tiles > 0)
-        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(tp.main_tiles * ngroups)), dim3(kThreads), kSmemP, st,
-                           x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, tp.main_tiles, ngroups, split2,
-                           stagger_for((Cin + kCK - 1) / kCK),
-                           TailSplit{tp.main_tiles / Bg, 0, 1, 0, nullptr});
-    if (tp.ksplit > 1) {
-        const int ntail = (int)nblk - tp.main_tiles;
-        float *ws = static_cast<float *>(workspace);
-        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(ntail * ngroups * tp.ksplit)), dim3(kThreads), kSmemP, st,
-                           x, up, bias, y, B, Cin, H, W, Cout, CoutP, tiles_x, tiles_y, bsx, bsy, slope, do_leaky, co0, ntail, ngroups, 0, stagger_for(tp.cps),
-                           TailSplit{ntail / Bg, tp.main_tiles / Bg, tp.ksplit, tp.cps, ws});
-        const int ncout = min(ngroups * G::kCoutT, Cout - co0);
-        const int64_t total = (int64_t)ntail * ncout * kTH * (GW / 4);
-        hipLaunchKernelGGL(wino4_tail_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st,
-                           ws, bias, y, tp.ksplit, ntail / Bg, tp.main_tiles / Bg, ntail, tiles_x, kTH, GW, IH, B, H, W, Cout, co0, ncout, bsy, slope,
-                           do_leaky, split2, total);
-    }
-    pwc::note_kernel("conv3x3_wino4p_kernel", CB, TG, GW, tp.ksplit, 1, IH);
-    return pwc::check_launch("conv3x3_wino4p_kernel");
-}
-
 // Tile-group width for a map of W columns: 64 unless that leaves the groups under 85 % full and 32 does better (the 14x32 lattice images of
 // dc_conv4: 0.5 vs 1.0)
 inline int wino4_gw(int W) {
@@ -784,6 +735,94 @@ inline W4Form wino4_form(int H, int W, int Cin, int tg) {
     return W4Form{gw, th, 0, 1};
 }
 
+// ---- the layer plan ---------------------------------------------------------------------------------------------------------------------
+// THE description of how a layer becomes launches: the rule (pwc_conv3x3_wino4_preferred), the scratch query
+// (pwc_conv3x3_wino4_workspace_bytes) and the launcher (pwc_conv3x3_wino4_fwd, launch_wino4) all read it and compute none of it again.
+// 64-cout workgroups (4 cout blocks x 2 tile groups) for as many pairs of 32-cout blocks as the padded layer has, one 32-cout launch
+// (2 x 4) for an odd rest; each in the form wino4_form picks for this map.
+struct W4Launch {
+    int tg;                       // tile groups per workgroup: 2 = the 64-cout launch <4, 2, ..>, 4 = the 32-cout one <2, 4, ..>
+    int co0, ngroups;             // first cout and cout groups of the launch (grid: nblk x ngroups workgroups)
+    W4Form form;
+    int Bg;                       // images -- stacked: groups of form.kimg images, over which the tile arithmetic (tail split, XCD order) runs
+    int tiles_x, tiles_y, nchunks;
+    int64_t nblk;                 // Bg x tiles_x x tiles_y
+    TailPlan tail;                // the Cin split as planned (the launcher runs unsplit when the caller's workspace does not serve it)
+    // for the rule: share of the workgroups' rows (stacked: of the padded image's) and columns inside the map, and whether the launch
+    // covers the chip -- one smaller than the chip counts with the input-channel slices of the whole-launch split (small batches),
+    // provided a slice keeps a K loop worth its fixed cost
+    double row_fill, col_fill;
+    bool covers;
+};
+struct W4Layer { int n; W4Launch l[2]; };
+
+inline W4Layer wino4_layer(int B, int Cin, int H, int W, int Cout, int split2) {
+    const int n32 = cout_padded4(Cout) / 32, nchunks = (Cin + kCK - 1) / kCK;
+    W4Layer layer{};
+    auto add = [&](int tg, int co0, int ngroups) {
+        const W4Form f = wino4_form(H, W, Cin, tg);
+        const int Bg = (B + f.kimg - 1) / f.kimg, tiles_x = (W + f.gw - 1) / f.gw, tiles_y = f.ih ? 1 : (H + f.th - 1) / f.th;
+        const int64_t nblk = (int64_t)Bg * tiles_x * tiles_y, nwg = nblk * ngroups;
+        bool covers = nwg >= 200;
+        if (!covers && pwc::option(pwc::OPT_W4_SMALLSPLIT)) {
+            const int k = wino4_small_ksplit(nwg, nchunks, device_cus());
+            covers = nwg * k >= pwc::option(pwc::OPT_W4_SMALL_MIN_WGS) && nchunks / k >= 6;
+        }
+        layer.l[layer.n++] = W4Launch{tg, co0, ngroups, f, Bg, tiles_x, tiles_y, nchunks, nblk,
+                                      wino4_tail_plan(Bg, nblk, ngroups, nchunks, Cout, f.th * f.gw, split2),
+                                      f.ih ? (double)H / f.ih : wino4_row_fill(H, f.th), (double)W / (tiles_x * f.gw), covers};
+    };
+    if (n32 >= 2) add(2, 0, n32 / 2);
+    if (n32 & 1) add(4, (n32 / 2) * 64, 1);
+    return layer;
+}
+
+// The staggered schedule pays in the K loop and costs at its ends (four specialisations of the unrolled body instead of two are
+// fetched): x1.02-1.04 from 24 chunks per workgroup up, x1.00 at 16, x0.96-0.98 at the 8-11 chunks of a slice of a small launch
+constexpr int kStaggerMinChunks = 16;
+
+// One launch record of the layer plan (the launcher's own part: what needs the template arguments, the caller's pointers or the stream)
+template <int CB, int TG, int GW, int IH = 0>
+int launch_wino4(const W4Launch &l, const pwc::WinoArgs &a) {
+    using G = Geo4<CB, TG, GW, IH>;
+    constexpr int kSmemP = G::kSmemBytes > 8 * 64 * 64 * 4 ? G::kSmemBytes : 8 * 64 * 64 * 4;       // rings, or the 128 KiB of the final exchange
+    static pwc::LdsAttrOnce once;
+    if (const int rc = pwc::ensure_lds_attr(once, reinterpret_cast<const void *>(&conv3x3_wino4p_kernel<CB, TG, GW, IH>), kSmemP, "conv3x3_wino4p_kernel"))
+        return rc;
+    if (IH && (a.H > IH || a.W > GW || a.Cin % kCK || (int64_t)(G::kImg - 1) * a.bsx * 4 + (int64_t)kCK * a.H * a.W * 4 > 0x7fffffffLL))
+        PWC_FAIL(PWC_EUNSUPPORTED, "pwc_conv3x3_wino4_fwd: stacked tile groups need H <= %d, W <= %d, Cin %% 4 == 0 and 31-bit offsets", IH, GW);
+    const int CoutP = cout_padded4(a.Cout);
+    constexpr int kTH = G::kTH;
+    // option "w4_stagger": 0 = every wave on the parent schedule, 1 = waves 4-7 staggered in the forms where that measured faster
+    // (Geo4::kStagger) and for workgroups of at least kStaggerMinChunks chunks, 2 = in every launch (measurements)
+    const int sopt = pwc::option(pwc::OPT_W4_STAGGER);
+    auto stagger_for = [&](int chunks) { return (sopt >= 2 || (sopt == 1 && G::kStagger && chunks >= kStaggerMinChunks)) ? 1 : 0; };
+    if (l.nblk * l.ngroups > 0x7fffffffLL) PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino4_fwd: grid too large");
+    // the planned Cin split needs the caller's workspace: without one that is large enough and 16-byte aligned the launch runs unsplit
+    TailPlan tp = l.tail;
+    if (tp.ksplit > 1 && (!a.ws || a.ws_bytes < tp.ws_bytes || (reinterpret_cast<uintptr_t>(a.ws) & 15u))) tp = TailPlan{(int)l.nblk, 1, 0, 0};
+    if (tp.main_tiles > 0)
+        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(tp.main_tiles * l.ngroups)), dim3(kThreads), kSmemP, a.st,
+                           a.x, a.up, a.bias, a.y, a.B, a.Cin, a.H, a.W, a.Cout, CoutP, l.tiles_x, l.tiles_y, a.bsx, a.bsy, a.slope, a.do_leaky, l.co0,
+                           tp.main_tiles, l.ngroups, a.split2, stagger_for(l.nchunks),
+                           TailSplit{tp.main_tiles / l.Bg, 0, 1, 0, nullptr});
+    if (tp.ksplit > 1) {
+        const int ntail = (int)l.nblk - tp.main_tiles;
+        float *ws = static_cast<float *>(a.ws);
+        hipLaunchKernelGGL((conv3x3_wino4p_kernel<CB, TG, GW, IH>), dim3((unsigned)(ntail * l.ngroups * tp.ksplit)), dim3(kThreads), kSmemP, a.st,
+                           a.x, a.up, a.bias, a.y, a.B, a.Cin, a.H, a.W, a.Cout, CoutP, l.tiles_x, l.tiles_y, a.bsx, a.bsy, a.slope, a.do_leaky, l.co0,
+                           ntail, l.ngroups, 0, stagger_for(tp.cps),
+                           TailSplit{ntail / l.Bg, tp.main_tiles / l.Bg, tp.ksplit, tp.cps, ws});
+        const int ncout = min(l.ngroups * G::kCoutT, a.Cout - l.co0);
+        const int64_t total = (int64_t)ntail * ncout * kTH * (GW / 4);
+        hipLaunchKernelGGL(wino4_tail_reduce_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.st,
+                           ws, a.bias, a.y, tp.ksplit, ntail / l.Bg, tp.main_tiles / l.Bg, ntail, l.tiles_x, kTH, GW, IH, a.B, a.H, a.W, a.Cout, l.co0, ncout,
+                           a.bsy, a.slope, a.do_leaky, a.split2, total);
+    }
+    pwc::note_kernel("conv3x3_wino4p_kernel", CB, TG, GW, tp.ksplit, 1, IH);
+    return pwc::check_launch("conv3x3_wino4p_kernel");
+}
+
 }  // namespace
 
 // Can this layer run here at all?  Dilation 1 (a dilated layer's lattices are not contiguous in memory: no 16-byte pieces),
@@ -795,32 +834,15 @@ static bool wino4_supported(int W, int dilation) { return dilation == 1 && W % 4
 // over (a workgroup costs ~10 us outside its K loop).  Option "conv_wino4" = 0 (pwc_set_option, default from PWC_CONV_WINO4) switches the route off (A/B runs).
 // Maps shorter than a workgroup count as filled when a stacked form serves them (wino4_form: the padded images fill it to H / ceil4(H),
 // and coverage counts groups of images); option "w4_stacked" = 0 (PWC_W4_STACKED) refuses those launches -- the round-4 rule.
+// EVERY launch of the layer's plan must pass -- conv3_2 (96 couts @56x128) fails on its 32-cout launch (128 workgroups, x0.94).
 extern "C" int pwc_conv3x3_wino4_preferred(int B, int Cin, int H, int W, int Cout, int dilation) {
     if (B <= 0 || Cin < 32 || H <= 0 || W <= 0 || Cout < 32 || !wino4_supported(W, dilation)) return 0;
-    const int knob = pwc::option(pwc::OPT_CONV_WINO4);
-    if (!knob) return 0;
-    const int n32 = cout_padded4(Cout) / 32;
-    const int nchunks = (Cin + kCK - 1) / kCK;
-    // every launch the layer splits into must cover the chip: the 64-cout launch (two tile groups per workgroup) and, for an odd number
-    // of 32-cout blocks, the 32-cout one (four groups) -- conv3_2 (96 couts @56x128) fails on the latter (128 workgroups, x0.94).  A launch
-    // smaller than the chip counts with the input-channel slices wino4_tail_plan cuts it into (small batches), provided a slice keeps
-    // a K loop worth its fixed cost.
-    auto covers = [&](int64_t nblk, int ngroups) {
-        const int64_t nwg = nblk * ngroups;
-        if (nwg >= 200) return true;
-        if (!pwc::option(pwc::OPT_W4_SMALLSPLIT)) return false;
-        const int k = wino4_small_ksplit(nwg, nchunks, device_cus());
-        return nwg * k >= pwc::option(pwc::OPT_W4_SMALL_MIN_WGS) && nchunks / k >= 6;
-    };
-    auto launch_ok = [&](int tg, int ngroups) {
-        const W4Form f = wino4_form(H, W, Cin, tg);
-        if (f.ih ? !pwc::option(pwc::OPT_W4_STACKED) : wino4_row_fill(H, f.th) < 0.85) return false;
-        const int tiles_x = (W + f.gw - 1) / f.gw;
-        const int64_t nblk = (int64_t)((B + f.kimg - 1) / f.kimg) * tiles_x * (f.ih ? 1 : (H + f.th - 1) / f.th);
-        return covers(nblk, ngroups) && (double)W / (tiles_x * f.gw) >= 0.85;
-    };
-    if (n32 >= 2 && !launch_ok(2, n32 / 2)) return 0;
-    if ((n32 & 1) && !launch_ok(4, 1)) return 0;
+    if (!pwc::option(pwc::OPT_CONV_WINO4)) return 0;
+    const W4Layer layer = wino4_layer(B, Cin, H, W, Cout, 0);
+    for (int i = 0; i < layer.n; ++i) {
+        const W4Launch &l = layer.l[i];
+        if (l.row_fill < 0.85 || l.col_fill < 0.85 || !l.covers || (l.form.ih && !pwc::option(pwc::OPT_W4_STACKED))) return 0;
+    }
     return 1;
 }
 
@@ -852,47 +874,29 @@ extern "C" int pwc_conv3x3_wino4_fwd(const void *x, const void *up, const void *
     if (x_bstride < Cin * plane || y_bstride < Cout * plane / ((flags & PWC_CONV_SPLIT2) ? 4 : 1))
         PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino4_fwd: batch stride smaller than the tensor");
     if (plane * kCK * 4 >= 0x7fffffffLL) PWC_FAIL(PWC_EUNSUPPORTED, "pwc_conv3x3_wino4_fwd: image plane too large for 32-bit DMA offsets");
-    const float *xf = static_cast<const float *>(x), *uf = static_cast<const float *>(up), *bf = static_cast<const float *>(bias);
-    float *yf = static_cast<float *>(y);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    const int do_leaky = (flags & PWC_ACT_LEAKY) ? 1 : 0;
     const int split2 = (flags & PWC_CONV_SPLIT2) ? 1 : 0;
     if (split2 && ((H & 1) || (W & 7) || (y_bstride & 1)))
         PWC_FAIL(PWC_EINVAL, "pwc_conv3x3_wino4_fwd: PWC_CONV_SPLIT2 needs even H, W %% 8 == 0 and an even batch stride");
-    const int n32 = cout_padded4(Cout) / 32;
-    // 64-cout workgroups (4 cout blocks x 2 tile groups) for as many pairs of 32 as there are, one 32-cout launch (2 x 4) for an odd rest;
-    // each in the form wino4_form picks for this map (stacked images where the map is shorter than the workgroup)
-#define PWC_W4_ARGS xf, uf, bf, yf, B, Cin, H, W, Cout, x_bstride, y_bstride, leaky_slope, do_leaky, st
-    if (n32 >= 2) {
-        const W4Form f = wino4_form(H, W, Cin, 2);
-        const int rc = f.ih ? launch_wino4<4, 2, 16, 8>(PWC_W4_ARGS, 0, n32 / 2, split2, workspace, workspace_bytes)
-                     : f.gw == 64 ? launch_wino4<4, 2, 64>(PWC_W4_ARGS, 0, n32 / 2, split2, workspace, workspace_bytes)
-                                  : launch_wino4<4, 2, 32>(PWC_W4_ARGS, 0, n32 / 2, split2, workspace, workspace_bytes);
+    const pwc::WinoArgs a{static_cast<const float *>(x), static_cast<const float *>(up), static_cast<const float *>(bias), static_cast<float *>(y),
+                          B, Cin, H, W, Cout, 1, x_bstride, y_bstride, leaky_slope, (flags & PWC_ACT_LEAKY) ? 1 : 0, split2,
+                          workspace, workspace_bytes, static_cast<hipStream_t>(stream)};
+    const W4Layer layer = wino4_layer(B, Cin, H, W, Cout, split2);
+    for (int i = 0; i < layer.n; ++i) {
+        const W4Launch &l = layer.l[i];
+        const int rc = l.tg == 2 ? (l.form.ih ? launch_wino4<4, 2, 16, 8>(l, a) : l.form.gw == 64 ? launch_wino4<4, 2, 64>(l, a) : launch_wino4<4, 2, 32>(l, a))
+                                 : (l.form.ih ? launch_wino4<2, 4, 32, 16>(l, a) : l.form.gw == 64 ? launch_wino4<2, 4, 64>(l, a) : launch_wino4<2, 4, 32>(l, a));
         if (rc) return rc;
     }
-    if (n32 & 1) {
-        const W4Form f = wino4_form(H, W, Cin, 4);
-        return f.ih ? launch_wino4<2, 4, 32, 16>(PWC_W4_ARGS, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes)
-             : f.gw == 64 ? launch_wino4<2, 4, 64>(PWC_W4_ARGS, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes)
-                          : launch_wino4<2, 4, 32>(PWC_W4_ARGS, (n32 / 2) * 64, 1, split2, workspace, workspace_bytes);
-    }
-#undef PWC_W4_ARGS
     return PWC_OK;
 }
 
-// Scratch for the tail / whole-launch split of launch_wino4 (0: neither applies to this layer's launches)
+// Scratch for the tail / whole-launch split of the layer's launches (0: neither applies).  Planned without PWC_CONV_SPLIT2 whatever the
+// caller will pass: a lattice-storing layer, which never tail-splits, is over-stated -- the plan's scratch buffer is sized by this answer.
 extern "C" int64_t pwc_conv3x3_wino4_workspace_bytes(int B, int Cin, int H, int W, int Cout) {
     if (B <= 0 || Cin <= 0 || H <= 0 || W <= 0 || Cout <= 0 || !wino4_supported(W, 1)) return 0;
-    const int n32 = cout_padded4(Cout) / 32, nchunks = (Cin + kCK - 1) / kCK;
-    auto need_of = [&](int tg, int ngroups) {                   // as launch_wino4 plans it, in the form the launcher picks
-        const W4Form f = wino4_form(H, W, Cin, tg);
-        const int Bg = (B + f.kimg - 1) / f.kimg;
-        const int64_t tiles_x = (W + f.gw - 1) / f.gw;
-        return wino4_tail_plan(Bg, (int64_t)Bg * tiles_x * (f.ih ? 1 : (H + f.th - 1) / f.th), ngroups, nchunks, Cout, f.th * f.gw, 0).ws_bytes;
-    };
+    const W4Layer layer = wino4_layer(B, Cin, H, W, Cout, 0);
     int64_t need = 0;
-    if (n32 >= 2) need = max(need, need_of(2, n32 / 2));
-    if (n32 & 1) need = max(need, need_of(4, 1));
+    for (int i = 0; i < layer.n; ++i) need = max(need, layer.l[i].tail.ws_bytes);
     return need;
 }
 

@@ -475,6 +475,15 @@ int launch(const float *x, int B, int Cin, int H, int W, int64_t bsx,
 
 inline bool al16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// What every streaming launch asks of the input: rows of whole, aligned 16-byte pieces, at least PWC_STREAM_MINW columns (default 64: the
+// 64-column maps of level 4 run half-filled 128-column tiles, still ahead of split-K MFMA head + deconv, -45 us), 31-bit plane offsets --
+// and at least min_tiles 8-row tiles, the one threshold in which the three predicates below differ
+inline bool stream_geometry_ok(int B, int H, int W, const void *x, int64_t bsx, int min_tiles) {
+    static const int min_w = [] { const char *e = getenv("PWC_STREAM_MINW"); return (e && *e) ? atoi(e) : 64; }();
+    return (W % 4 == 0) && (W >= min_w) && al16(x) && (bsx % 4 == 0) && ((int64_t)H * W * kCK * 4 < 0x7fffffffLL) &&
+           (int64_t)B * ((W + kTW - 1) / kTW) * ((H + 7) / 8) >= min_tiles;
+}
+
 }  // namespace
 
 namespace pwc_conv {
@@ -491,23 +500,17 @@ int64_t stream3x3_head_upfeat_workspace_bytes(int B, int Cin, int H, int W) {
 // head + upfeat below stream3x3_ok's 64 tiles: possible with Cin slices and the caller's workspace (the plan decides whether it beats
 // the 10-channel convolution there: option "head_sliced_min_tiles", read by the Python engine)
 bool stream3x3_head_upfeat_sliced_ok(int B, int Cin, int H, int W, const void *x, int64_t bsx, const void *ws, int64_t ws_bytes) {
-    static const int min_w = [] { const char *e = getenv("PWC_STREAM_MINW"); return (e && *e) ? atoi(e) : 64; }();
     const SlicePlan sp = slice_plan(B, Cin, H, W, 256);
-    return sp.nslice > 1 && ws && al16(ws) && ws_bytes >= slice_ws_bytes<MODE_HEAD | MODE_UPFEAT>(sp, B, H, W) && (W % 4 == 0) && (W >= min_w) &&
-           al16(x) && (bsx % 4 == 0) && ((int64_t)H * W * kCK * 4 < 0x7fffffffLL) && (int64_t)B * ((W + kTW - 1) / kTW) * ((H + 7) / 8) >= 4;
+    return sp.nslice > 1 && ws && al16(ws) && ws_bytes >= slice_ws_bytes<MODE_HEAD | MODE_UPFEAT>(sp, B, H, W) && stream_geometry_ok(B, H, W, x, bsx, 4);
 }
 
 bool stream3x3_head_sliced_ok(int B, int Cin, int H, int W, const void *x, int64_t bsx, const void *ws, int64_t ws_bytes) {
-    static const int min_w = [] { const char *e = getenv("PWC_STREAM_MINW"); return (e && *e) ? atoi(e) : 64; }();
     const SlicePlan sp = slice_plan(B, Cin, H, W);
-    return sp.nslice > 1 && ws && al16(ws) && ws_bytes >= slice_ws_bytes<MODE_HEAD>(sp, B, H, W) && (W % 4 == 0) && (W >= min_w) && al16(x) &&
-           (bsx % 4 == 0) && ((int64_t)H * W * kCK * 4 < 0x7fffffffLL) && (int64_t)B * ((W + kTW - 1) / kTW) * ((H + 7) / 8) >= 8;
+    return sp.nslice > 1 && ws && al16(ws) && ws_bytes >= slice_ws_bytes<MODE_HEAD>(sp, B, H, W) && stream_geometry_ok(B, H, W, x, bsx, 8);
 }
 
 bool stream3x3_ok(int B, int Cin, int H, int W, const void *x, int64_t bsx) {
-    static const int min_w = [] { const char *e = getenv("PWC_STREAM_MINW"); return (e && *e) ? atoi(e) : 64; }();    // 64-column maps (level 4) run half-filled 128-column tiles: still ahead of split-K MFMA head + deconv (-45 us)
-    return (W % 4 == 0) && (W >= min_w) && al16(x) && (bsx % 4 == 0) && ((int64_t)H * W * kCK * 4 < 0x7fffffffLL) &&
-           (int64_t)B * ((W + kTW - 1) / kTW) * ((H + 7) / 8) >= 64;    // fewer: the split-K MFMA head + deconv kernel win (24 measured: -1.6 % at batch 4)
+    return stream_geometry_ok(B, H, W, x, bsx, 64);    // fewer tiles: the split-K MFMA head + deconv kernel win (24 measured: -1.6 % at batch 4)
 }
 
 // w = packed head taps [Cin][20] (tail of pwc_conv3x3_pack's buffer for Cout == 2)
