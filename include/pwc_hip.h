@@ -32,6 +32,7 @@
  *                       train_fundamental.py:397-428 (the no-ground-truth validation metrics, on two given flows)
  *   pwc_flow_stats / pwc_flow_color   flow_to_color pwc_extract_flow.py:58-123 (the colour-wheel image save_outputs writes, :182-190)
  *                       and calculate_dominant_direction topview.py:122-134
+ *   pwc_flow_compare    compare_flows / print_flow_stats onnx_pth_compare.py:133-201, :225-230 (the parity report of two flow fields)
  *   pwc_flow_quiver     the arrow grid of create_quiver_frame pwc_extract_flow_video.py:94-135 and draw_flow_arrows topview.py:137-178
  *                       (vectors, tips and flags; drawing stays with the caller)
  *   pwc_kitti_augment   KittiFlowDataset.__getitem__ data_processing_or.py:228-294 (reduced augmentation with cv2.warpAffine, random
@@ -538,6 +539,74 @@ int pwc_kitti_score(const void *flow_q, int n, int Hq, int Wq, int crop_h, int c
                     const void *gt, int gt_kind, const void *valid,
                     void *flow_out /* may be NULL */, void *workspace, int64_t workspace_bytes,
                     void *out /* float [n][2] */, void *stream);
+
+/* Flow-comparison report on the device (additions within ABI v13, csrc/pwc_flow_compare.hip): compare_flows and print_flow_stats of
+ * onnx_pth_compare.py:133-201, :225-230 in one launch pair.  a (the reference side, "pth") and b are f32 [n][2][H][W]; each sample's
+ * [2][H][W] is contiguous, the batch strides (in elements, >= 2*H*W) are free and separate.  Per pixel, fp32 with no fused
+ * multiply-add, square root correctly rounded:
+ *   du = a_u - b_u;  dv = a_v - b_v;  epe = sqrtf(du*du + dv*dv)      -- bit for bit the reference's float32 np.linalg.norm(a - b, axis=-1)
+ * Per scalar (2 per pixel) the f32 values d = a - b, a, b are widened to fp64 and d*d, |d|, a*a, b*b, |a|, a, b, a*b are added in
+ * fp64; epe is added in fp64 per pixel.  max |d|, max epe and min / max of a and of b are exact f32 reductions; count_k is the
+ * number of pixels with epe <= taus[k] (inclusive, f32 comparison).  taus: HOST array of ntau (1..PWC_FLOW_COMPARE_MAX_TAUS) finite
+ * non-negative floats, read during the call and passed to the kernel by value.
+ * out (device, 8-byte aligned): double [n + 1][PWC_FLOW_COMPARE_FIELDS].  Row s < n is sample s; row n is the whole batch, which is
+ * the reference called on the samples stacked along H.  With N = 2*H*W*(samples in the row) and P = N / 2, all formed in fp64 from
+ * the totals:
+ *   L2 = sqrt(S d^2)   MAE = S|d| / N   REL_L2 = L2 / (sqrt(S a^2) + 1e-8)   REL_MAE = MAE / (S|a| / N + 1e-8)
+ *   COSINE = S ab / (sqrt(S a^2) * sqrt(S b^2) + 1e-8)
+ *   PEARSON = (S ab - S a * S b / N) / sqrt((S a^2 - (S a)^2 / N) * (S b^2 - (S b)^2 / N)), clipped to [-1, 1] as np.corrcoef does;
+ *             NaN when min == max for either field (np.corrcoef's NaN; the exact test keeps rounding from turning it into noise)
+ *   EPE_MEAN = S epe / P   AGREE_k = (double)count_k / P * 100.0 (the reference's (vec_diff <= tau).mean() * 100.0 bit for bit;
+ *             NaN for k >= ntau)
+ *   MEAN_A = S a / N, STD_A = sqrt(max(S a^2 / N - MEAN_A^2, 0)), exactly 0 when min == max; MEAN_B / STD_B alike (population std)
+ * NaN / Inf inputs are not special-cased: the sums carry them as IEEE arithmetic dictates, epe <= tau is false for a NaN epe, and
+ * the extrema come from fmaxf, which returns the other operand when one is NaN (np.max would return NaN).
+ * epe_map: NULL, or float [n][H][W] (dense) that receives the per-pixel epe; the record is the same bits with and without it.
+ * Each 32 x 128 tile leaves its totals (fixed tree order) in the workspace; the finish kernel's workgroup s < n adds the tiles of
+ * sample s in tile order, workgroup n adds every tile in (sample, tile) order: no atomics, bit-reproducible, no allocation, no host
+ * synchronisation, no host callback -- the call can be captured in a graph (taus are captured by value).
+ * workspace: device, 8-byte aligned, pwc_flow_compare_workspace_bytes(n, H, W) = 128 * n * tiles per sample bytes (-1 for a
+ * non-positive size).
+ * PWC_EINVAL, nothing launched: a null a / b / taus / workspace / out, non-positive sizes, ntau outside 1..8, a tau that is negative,
+ * NaN or infinite, n*2*H*W >= 2^31, n > 65535, H > 32 * 65535, a batch stride < 2*H*W, a workspace that is too small, workspace / out
+ * not 8-byte aligned, a / b / epe_map not 4-byte aligned. */
+#define PWC_FLOW_COMPARE_MAX_TAUS 8
+#define PWC_FLOW_COMPARE_FIELDS 44
+#define PWC_FC_N 0         /* scalars in the row, as a double */
+#define PWC_FC_P 1         /* pixels in the row */
+#define PWC_FC_SUM_D2 2
+#define PWC_FC_SUM_ABS_D 3
+#define PWC_FC_SUM_A2 4
+#define PWC_FC_SUM_B2 5
+#define PWC_FC_SUM_ABS_A 6
+#define PWC_FC_SUM_A 7
+#define PWC_FC_SUM_B 8
+#define PWC_FC_SUM_AB 9
+#define PWC_FC_SUM_EPE 10
+#define PWC_FC_MAX_ABS 11  /* "Max abs diff" */
+#define PWC_FC_EPE_MAX 12
+#define PWC_FC_MIN_A 13
+#define PWC_FC_MAX_A 14
+#define PWC_FC_MIN_B 15
+#define PWC_FC_MAX_B 16
+#define PWC_FC_COUNT0 17   /* 17..24: count_k as a double (exact), 0 for k >= ntau */
+#define PWC_FC_L2 25
+#define PWC_FC_MAE 26
+#define PWC_FC_REL_L2 27
+#define PWC_FC_REL_MAE 28
+#define PWC_FC_PEARSON 29
+#define PWC_FC_COSINE 30
+#define PWC_FC_EPE_MEAN 31
+#define PWC_FC_AGREE0 32   /* 32..39: agreement in percent */
+#define PWC_FC_MEAN_A 40
+#define PWC_FC_STD_A 41
+#define PWC_FC_MEAN_B 42
+#define PWC_FC_STD_B 43
+int64_t pwc_flow_compare_workspace_bytes(int n, int H, int W);
+int pwc_flow_compare(const void *a, const void *b, int n, int H, int W, int64_t a_bstride, int64_t b_bstride,
+                     const float *taus /* host */, int ntau, void *epe_map /* may be NULL */,
+                     void *workspace, int64_t workspace_bytes,
+                     void *out /* double [n + 1][PWC_FLOW_COMPARE_FIELDS] */, void *stream);
 
 /* Flow pictures on the device (additions within ABI v13, csrc/pwc_flowviz.hip).  All three read the top-left crop_h x crop_w of
  * flow [n][2][Hq][Wq] f32 (dense planes, batch stride in elements): the reference colours and draws the cropped quarter-resolution

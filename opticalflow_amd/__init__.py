@@ -17,5 +17,7 @@ from . import pil_resize  # noqa: F401
 from .pil_resize import resize_flow, resize_frames  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import FusedAdam, FusedAdamW  # noqa: F401
+from . import compare  # noqa: F401
+from .compare import compare_flows  # noqa: F401
 
 __version__ = "0.1.0"

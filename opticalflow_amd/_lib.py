@@ -110,6 +110,9 @@ SIGNATURES = {
     "pwc_kitti_score_workspace_bytes": (c_int64, [c_int] * 3),
     "pwc_kitti_score": (c_int, [c_void_p] + [c_int] * 7 + [c_int64, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int64,
                                 c_void_p, c_void_p]),
+    "pwc_flow_compare_workspace_bytes": (c_int64, [c_int] * 3),
+    "pwc_flow_compare": (c_int, [c_void_p, c_void_p] + [c_int] * 3 + [c_int64, c_int64, ctypes.POINTER(c_float), c_int, c_void_p, c_void_p,
+                                 c_int64, c_void_p, c_void_p]),
     "pwc_flow_stats_workspace_bytes": (c_int64, [c_int] * 3),
     "pwc_flow_stats": (c_int, [c_void_p] + [c_int] * 5 + [c_int64, c_int, c_float, c_float, c_void_p, c_int64, c_void_p, c_void_p]),
     "pwc_flow_color": (c_int, [c_void_p] + [c_int] * 5 + [c_int64, c_int, c_float, c_void_p, c_void_p, c_void_p]),

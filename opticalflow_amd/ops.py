@@ -607,6 +607,80 @@ def kitti_score(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, out_
     return out
 
 
+# record layout of pwc_flow_compare (include/pwc_hip.h PWC_FC_*): one float64 row per sample, then the batch row
+FLOW_COMPARE_MAX_TAUS = 8
+FLOW_COMPARE_FIELDS = 44
+FC_N, FC_P, FC_SUM_D2, FC_SUM_ABS_D, FC_SUM_A2, FC_SUM_B2, FC_SUM_ABS_A, FC_SUM_A, FC_SUM_B, FC_SUM_AB, FC_SUM_EPE = range(11)
+FC_MAX_ABS, FC_EPE_MAX, FC_MIN_A, FC_MAX_A, FC_MIN_B, FC_MAX_B = range(11, 17)
+FC_COUNT0 = 17
+FC_L2, FC_MAE, FC_REL_L2, FC_REL_MAE, FC_PEARSON, FC_COSINE, FC_EPE_MEAN = range(25, 32)
+FC_AGREE0 = 32
+FC_MEAN_A, FC_STD_A, FC_MEAN_B, FC_STD_B = range(40, 44)
+
+
+def flow_compare_workspace_bytes(n: int, H: int, W: int) -> int:
+    return _query_bytes(_lib.load().pwc_flow_compare_workspace_bytes(n, H, W), "flow-compare")
+
+
+def _compare_flow_arg(t: torch.Tensor, name: str) -> int:
+    """One side of flow_compare: float32 device [n,2,H,W] with dense planes -> batch stride in elements."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.shape[1] != 2:
+        raise ValueError("%s must be a tensor [n,2,H,W], got %s" % (name, tuple(getattr(t, "shape", ()))))
+    if t.dtype in (torch.float16, torch.bfloat16):
+        raise TypeError("%s is %s: flow_compare reads float32 only (widen a half-precision flow with .float() first; the report "
+                        "is defined on float32 values)" % (name, t.dtype))
+    if t.dtype != torch.float32:
+        raise TypeError("%s must be float32, got %s" % (name, t.dtype))
+    return _plane_dense(t, name)
+
+
+def flow_compare_taus(taus) -> Tuple[float, ...]:
+    """The thresholds of flow_compare as a tuple of Python floats, checked: 1..8 finite non-negative values."""
+    taus = tuple(float(t) for t in taus)
+    if not 1 <= len(taus) <= FLOW_COMPARE_MAX_TAUS:
+        raise ValueError("flow_compare takes 1..%d thresholds, got %d" % (FLOW_COMPARE_MAX_TAUS, len(taus)))
+    for t in taus:
+        if not (t >= 0.0 and math.isfinite(t)):
+            raise ValueError("thresholds must be finite and non-negative, got %r" % (t,))
+    return taus
+
+
+def flow_compare(a: torch.Tensor, b: torch.Tensor, taus=(0.25, 0.5, 1.0, 2.0), epe_map: Optional[torch.Tensor] = None,
+                 workspace: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float64 [n+1, FLOW_COMPARE_FIELDS] record of pwc_flow_compare: compare_flows / print_flow_stats of onnx_pth_compare.py for the
+    float32 device flows a (the reference side) and b, [n,2,H,W] with dense planes and free batch strides.  Row s < n is sample s,
+    row n the whole batch (the samples stacked along H); columns are the FC_* indices.  taus: 1..8 EPE thresholds (agreement is
+    epe <= tau, compared in float32).  epe_map: optional contiguous float32 [n,H,W] that receives the per-pixel EPE.  workspace:
+    optional device tensor of flow_compare_workspace_bytes(n, H, W) bytes, 8-byte aligned (allocated when absent).  Device tensors
+    only, no host synchronisation, bit-reproducible, capturable in a graph when workspace and out are given."""
+    bsa = _compare_flow_arg(a, "a")
+    bsb = _compare_flow_arg(b, "b")
+    if tuple(a.shape) != tuple(b.shape) or a.device != b.device:
+        raise ValueError("a and b must have one shape and device, got %s on %s and %s on %s"
+                         % (tuple(a.shape), a.device, tuple(b.shape), b.device))
+    n, _, H, W = a.shape
+    if n < 1 or H < 1 or W < 1:
+        raise ValueError("flow_compare needs a non-empty [n,2,H,W], got %s" % (tuple(a.shape),))
+    taus = flow_compare_taus(taus)
+    dev = a.device
+    if epe_map is not None and (tuple(epe_map.shape) != (n, H, W) or epe_map.dtype != torch.float32 or epe_map.device != dev
+                                or not epe_map.is_contiguous()):
+        raise ValueError("epe_map must be contiguous float32 %s on %s" % ((n, H, W), dev))
+    out = _out_arg(out, (n + 1, FLOW_COMPARE_FIELDS), torch.float64, dev, contiguous=True)
+    need = flow_compare_workspace_bytes(n, H, W)
+    if workspace is None:
+        workspace, _ = _scratch(need, dev)
+    wp, wb = _workspace_args(workspace, a)
+    if wb < need:
+        raise ValueError("workspace has %d bytes, flow_compare needs %d" % (wb, need))
+    tau_arr = (ctypes.c_float * len(taus))(*taus)
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_flow_compare(a.data_ptr(), b.data_ptr(), n, H, W, bsa, bsb, tau_arr, len(taus), _ptr(epe_map), wp, wb,
+                                          out.data_ptr(), _stream(a))
+    check(rc, "pwc_flow_compare")
+    return out
+
+
 def _flow_crop_arg(flow: torch.Tensor, crop) -> Tuple[int, int, int, int, int, int]:
     """The [n,2,Hq,Wq] float32 device flow of the picture operators and its top-left crop -> (n, Hq, Wq, crop_h, crop_w, batch stride)."""
     if flow.dim() != 4 or flow.shape[1] != 2:
