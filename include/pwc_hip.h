@@ -661,9 +661,16 @@ int pwc_flow_quiver(const void *flow, int n, int Hq, int Wq, int crop_h, int cro
 /* Vanishing point of a flow field (additions within ABI v13, csrc/pwc_vanishing.hip): estimate_vanishing_point_from_flow of
  * pwc_extract_flow_video_vanishpoint.py:93-255 per frame, from vec float [n][gy][gx][2] as pwc_flow_quiver writes it ((dx, dy) in frame
  * pixels at x = gx*step, y = gy*step; gy = ceil(frame_h / step), gx alike).  fp64 throughout, no fused multiply-add.
- *   select   dx, dy widened; mag = hypot(dx, dy); a cell is kept when mag >= min_mag; N = number kept.  N <= max_points: all kept cells
- *            in row-major order.  N > max_points: the kept cells in the sequence of `order` (int32, a permutation of the gy*gx cells;
- *            entries outside 0 .. gy*gx-1 are skipped), the first max_points of them, in that sequence.  N < 5: status 2.
+ *   select   dx, dy widened; mag = hypot(dx, dy); a cell is kept when mag >= min_mag AND mag is finite; N = number kept.  This departs
+ *            from the reference, whose `mag < min_mag: continue` keeps a NaN magnitude (which then poisons its median and costs it the
+ *            refinement) and an infinite one: here a cell with a NaN or an infinite component counts as a cell below min_mag, and
+ *            the frame is answered from the others.  N <= max_points: all kept cells
+ *            in row-major order.  N > max_points: the kept cells in the sequence of `order` (int32, a permutation of the gy*gx cells),
+ *            the first max_points of them, in that sequence.  An `order` that is no permutation is read as it stands: an entry
+ *            outside 0 .. gy*gx-1 or naming a cell that is not kept is skipped; an entry that repeats an earlier one selects its
+ *            cell AGAIN (nothing records what was selected; the two copies are parallel, so they add no pair of their own, but each
+ *            pairs with every other line); and when the table names fewer than max_points kept cells, N used is that number.
+ *            N used < 5: status 2.
  *   pairs    for i < j in the selected order, with (dxn, dyn) = (dx / mag, dy / mag):
  *                 denom = d1x*d2y - d1y*d2x;  skipped when fabs(denom) < 1e-6;
  *                 t1 = ((p2x - p1x)*d2y - (p2y - p1y)*d2x) / denom;  ix = p1x + t1*d1x;  iy = p1y + t1*d1y;

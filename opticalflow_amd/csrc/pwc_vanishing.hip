@@ -2,7 +2,7 @@
 // batched, from the arrow grid pwc_flow_quiver leaves (vec float [n][Gy][Gx][2] = (dx, dy) at x = gx*step, y = gy*step).  All
 // arithmetic is fp64 with no contraction, the expressions spelled out in include/pwc_hip.h.  Three launches per call:
 //
-//   select_kernel  one workgroup per frame: zeroes the frame's histogram, counts the cells with hypot(dx, dy) >= min_mag (N), and
+//   select_kernel  one workgroup per frame: zeroes the frame's histogram, counts the cells with a finite hypot(dx, dy) >= min_mag (N), and
 //                  writes the selected cells in order: all of them row-major when N <= max_points (as the reference does), else the
 //                  first max_points kept cells in the sequence of `order` (a permutation of the cells; the reference draws from
 //                  NumPy's global state there, which nobody can reproduce).  The compaction is a ballot scan over 256 positions at a
@@ -72,6 +72,10 @@ __device__ __forceinline__ double cell_mag(const Vp &p, int b, int cell, double 
     return hypot(*dx, *dy);
 }
 
+// the selection's one predicate: at least min_mag and finite.  A NaN magnitude fails the first test by itself; an infinite one would
+// pass it, become the frame's largest magnitude and turn every weight of the frame into 0 or NaN.
+__device__ __forceinline__ bool mag_kept(double mag, double min_mag) { return mag >= min_mag && isfinite(mag); }
+
 // edge k of np.linspace(lo, hi, grid + 1): k * step + lo in two roundings, the last edge hi itself
 __device__ __forceinline__ double edge(int k, int grid, double lo, double hi, double step) { return k < grid ? (double)k * step + lo : hi; }
 
@@ -94,7 +98,7 @@ __global__ __launch_bounds__(kThreads) void select_kernel(Vp p) {
     for (int i = tid; i < p.grid * p.grid; i += kThreads) hist[i] = 0;
     long long cnt[1] = {0};
     double dx, dy;
-    for (int c = tid; c < p.cells; c += kThreads) cnt[0] += cell_mag(p, b, c, &dx, &dy) >= p.min_mag ? 1 : 0;
+    for (int c = tid; c < p.cells; c += kThreads) cnt[0] += mag_kept(cell_mag(p, b, c, &dx, &dy), p.min_mag) ? 1 : 0;
     pwc::tree_sum(redn, static_cast<double *>(nullptr), cnt);
     const int n_kept = (int)cnt[0];
     const bool by_order = n_kept > p.max_points;             // the entry point has made sure that `order` is there when this can happen
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(kThreads) void select_kernel(Vp p) {
         bool keep = false;
         if (pos < p.cells) {
             cell = by_order ? p.order[pos] : pos;
-            keep = (unsigned)cell < (unsigned)p.cells && cell_mag(p, b, cell, &dx, &dy) >= p.min_mag;
+            keep = (unsigned)cell < (unsigned)p.cells && mag_kept(cell_mag(p, b, cell, &dx, &dy), p.min_mag);
         }
         const unsigned long long m = __ballot(keep);
         if (lane == 0) wave_cnt[wv] = __popcll(m);

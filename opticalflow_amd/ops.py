@@ -794,8 +794,9 @@ def vanishing_point(vec: torch.Tensor, frame_h: int, frame_w: int, step: int, mi
     pairs kept, best gx, best gy, inliers) from the arrow grid vec float32 [n,Gy,Gx,2] of flow_quiver for the same frame and step.
     status 0 refined, 1 bin centre kept, 2 fewer than 5 vectors, 3 fewer than min_pairs intersections, 4 empty histogram; the vp row
     of a status >= 2 is (NaN, NaN, 0, NaN, NaN).  order: int32 permutation of the Gy*Gx cells on the device, required when there are
-    more cells than max_points (it decides which kept cells are used when more than max_points are kept).  vec must be contiguous: a
-    strided view is refused, not copied.  workspace: optional device tensor of vanishing_workspace_bytes(n, Gy, Gx, grid) bytes.
+    more cells than max_points (it decides which kept cells are used when more than max_points are kept; what a table that is no
+    permutation does is spelled out in include/pwc_hip.h).  A cell with a NaN or infinite component is dropped like one below min_mag.
+    vec must be contiguous: a strided view is refused, not copied.  workspace: optional device tensor of vanishing_workspace_bytes(n, Gy, Gx, grid) bytes.
     Device tensors only, no host synchronisation, bit-reproducible."""
     frame_h, frame_w, step, max_points, grid, min_pairs = int(frame_h), int(frame_w), int(step), int(max_points), int(grid), int(min_pairs)
     if frame_h < 1 or frame_w < 1:

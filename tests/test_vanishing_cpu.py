@@ -1,6 +1,7 @@
 """Vanishing points without a GPU: the NumPy oracle (tests/vanishing_oracle.py) against the reference's own return values
 (tests/golden/g16_vanishing.npz, written by tools/gen_golden_vanishing.py), the margin conditions that make every discrete outcome of
-a fixture case safe, the device's subsample rule, the C ABI additions and the wrappers' argument checks."""
+a fixture case safe, the device's subsample rule, the C ABI additions and the wrappers' argument checks; and the same three fixture
+checks for the edge cases (VO.EDGE_CASES, tests/golden/g19_vanishing_edges.npz), which tests/test_gpu_vanishing_edges.py runs."""
 import ctypes
 import os
 import re
@@ -180,3 +181,124 @@ def test_wrapper_argument_errors_raise_without_a_device():
     with pytest.raises(ValueError):
         ops.vanishing_workspace_bytes(1, 6, 8, 1)
     assert ops.vanishing_workspace_bytes(2, 6, 8, 64) == 2 * (24 + 8 * 64 * 64 + 4096)
+
+
+# ---- the edge cases: tests/golden/g19_vanishing_edges.npz (tools/gen_golden_vanishing.py edges), VO.EDGE_CASES ----
+
+@pytest.fixture(scope="module")
+def edge_gold():
+    path = os.path.join(HERE, "golden", "g19_vanishing_edges.npz")
+    assert os.path.getsize(path) <= 1 << 20
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files}
+
+
+@pytest.fixture(scope="module")
+def edge_results(edge_gold):
+    """The oracle on every edge case, computed once."""
+    out = {}
+    for name, c in VO.EDGE_CASES.items():
+        idx = edge_gold["idx/" + name] if edge_gold["idx/" + name].size else None
+        out[name] = VO.estimate(edge_gold["vec/" + name], c["frame"], c["step"], c["min_mag"], c["max_points"], c["grid_size"],
+                                c["min_pairs"], idx=idx)
+    return out
+
+
+@pytest.mark.parametrize("case", sorted(VO.EDGE_CASES))
+def test_oracle_reproduces_the_reference_on_the_edge_cases(edge_gold, edge_results, case):
+    r = edge_results[case]
+    assert edge_gold["vec/" + case].shape == VO.grid_shape(VO.EDGE_CASES[case]["frame"], VO.EDGE_CASES[case]["step"]) + (2,)
+    assert np.array_equal(edge_gold["vec/" + case], VO.make_field(case, int(edge_gold["seed/" + case])))
+    assert bool(edge_gold["ref_ok/" + case]) and r["status"] <= 1        # every edge case is one the reference answers
+    vx, vy, prob = edge_gold["ref/" + case]
+    assert _rel(vx, r["xy"][0]) <= 1e-12 and _rel(vy, r["xy"][1]) <= 1e-12 and _rel(prob, r["prob"]) <= 1e-12
+
+
+@pytest.mark.parametrize("case", sorted(VO.EDGE_CASES))
+def test_margin_conditions_hold_on_the_edge_cases(edge_results, case):
+    r = edge_results[case]
+    m = VO.edge_margins(r, case)
+    assert set(m) == {"mag", "denom", "range", "edges", "best", "inlier", "mag_ratio", "cond", "normal_eq"}
+    assert all(m.values()), [k for k, v in m.items() if not v]
+    frac = VO.normal_equations_fraction(r)
+    print("case %s: normal equations at %.3g of the xy tolerance" % (case, frac))
+    assert frac <= 0.1
+    if case in VO.EXACT_EDGE_CASES:                     # what replaces "mag" and "best" there: axis-aligned vectors of magnitude 0, 1, 2
+        vec = r["vec"].reshape(-1, 2).astype(np.float64)
+        below = float(np.nextafter(np.float32(2.0), np.float32(0.0)))
+        assert ((vec == 0).any(axis=1)).all() and np.isin(np.abs(vec).max(axis=1), [0.0, 1.0, 2.0, below]).all()
+        assert np.array_equal(r["mag_all"], np.abs(vec).max(axis=1)) and len(set(r["mags"].tolist())) == 1
+        assert np.array_equal(r["hist"], np.round(r["hist"]))
+    else:                                               # no exemption anywhere else: the plain rules, spelled out
+        c = VO.EDGE_CASES[case]
+        assert (np.abs(r["mag_all"] - c["min_mag"]) > 1e-6 * c["min_mag"]).all()
+        assert r["best_weight"] >= (1.0 + 1e-6) * r["runner_up"]
+
+
+def test_edge_cases_show_what_they_are_there_for(edge_gold, edge_results):
+    r, E = edge_results, VO.EDGE_CASES
+    # the cut of the by-order compaction (256 positions per round, 64 per wave)
+    for case, rounds in (("p768", (1,)), ("p1792", range(2, 7))):
+        keep, idx = r[case]["keep"], edge_gold["idx/" + case]
+        assert keep.size == {"p768": 768, "p1792": 1792}[case] and r[case]["n_kept"] > 700 and r[case]["n_used"] == 300 == len(idx)
+        order = VO.order_from_idx_interleaved(keep, idx)
+        assert np.array_equal(np.sort(order), np.arange(keep.size))
+        assert np.array_equal(VO.select_by_order(keep, order, 300), r[case]["cells"])
+        cut = VO.cut_position(keep, order, 300)
+        assert cut // 256 in rounds and cut % 64 != 0, (case, cut)
+        assert keep[order[cut]] and keep[order[:cut + 1]].sum() == 300
+    assert r["plus1"]["n_kept"] == E["plus1"]["max_points"] + 1 == r["plus1"]["n_used"] + 1 and r["plus1"]["keep"].size == 192
+    H, W = E["full1024"]["frame"]
+    assert H > W and r["full1024"]["keep"].size == 2048 and r["full1024"]["n_kept"] > 1024 and r["full1024"]["n_used"] == 1024
+    assert len(r["full1024"]["denom"]) == 523776 and edge_gold["vec/full1024"].shape == (64, 32, 2)
+    assert r["n5"]["n_kept"] == r["n5"]["n_used"] == 5 and r["n5"]["status"] in (0, 1) and E["n5"]["min_pairs"] == 5
+    assert r["n5"]["pairs_kept"] >= 5
+    mags = np.sort(r["n5"]["mags"])
+    raised = 0.5 * (mags[0] + mags[1])                  # above the weakest of the five: four are left
+    assert mags[0] * (1 + 1e-6) < raised < mags[1] * (1 - 1e-6)
+    c = E["n5"]
+    assert VO.estimate(edge_gold["vec/n5"], c["frame"], c["step"], raised, c["max_points"], c["grid_size"], c["min_pairs"])["status"] == 2
+    assert r["st1"]["status"] == 1 and 5 <= r["st1"]["n_kept"] <= 8 and r["st1"]["inliers"] < 5 and r["st1"]["xy"] == r["st1"]["center"]
+    assert r["st1"]["pairs_kept"] >= E["st1"]["min_pairs"]
+    assert edge_gold["vec/wide"].shape == (1, 65536, 2) and r["wide"]["status"] == 0 and r["wide"]["n_used"] == 1024 < r["wide"]["n_kept"]
+    assert 0 in r["wide"]["cells"] and 65535 in r["wide"]["cells"] and 1400 < r["wide"]["n_kept"] < 1600
+    assert (edge_gold["vec/wide"][0, ~r["wide"]["keep"]] == 0).all()
+    for case in VO.TIE_CASES:                           # the maximum attained at least twice, exactly
+        t = VO.tie_bins(r[case])
+        h = r[case]["hist"].ravel()
+        assert len(t) >= 2 and h[t[0]] == h[t[1]] == r[case]["best_weight"] == r[case]["runner_up"] and r[case]["status"] == 0
+        assert r[case]["best"] == tuple(int(v) for v in np.unravel_index(t[0], r[case]["hist"].shape))
+    # which lanes of the arg-max hold the two lowest tied bins (VO.tie_lanes says why each grid gives what it gives)
+    a, b = VO.tie_lanes(r["tie"])
+    assert a == b and VO.tie_bins(r["tie"])[1] - VO.tie_bins(r["tie"])[0] >= 256      # one lane walks both: its ascending scan decides
+    a, b = VO.tie_lanes(r["tie16"])
+    assert a < b and r["tie16"]["hist"].size == 256                                      # one bin per lane: only the tree decides
+    a, b = VO.tie_lanes(r["tie32"])
+    assert a > b and VO.tie_tree_sides(r["tie32"]) == (1, 0)                             # lower index, higher lane, upper side of the tree
+    assert VO.tie_tree_sides(r["tie"]) is None
+    m = r["atmin"]["mag_all"]
+    below = float(np.nextafter(np.float32(2.0), np.float32(0.0)))
+    assert E["atmin"]["min_mag"] == 2.0 and r["atmin"]["n_kept"] == (m == 2.0).sum() > 0 and (m == 1.0).any() and (m == below).any()
+    assert set(np.unique(m).tolist()) <= {0.0, 1.0, below, 2.0}
+
+
+def test_selection_rule_for_an_order_that_is_no_permutation():
+    keep = np.array([1, 0, 1, 1, 0, 1, 1, 1], bool)
+    order = np.array([7, -1, 8, 2 ** 30, 1, 2, 7, 4, 3, 0], np.int64)        # outside the grid: skipped; not kept: skipped; 7 twice
+    assert VO.select_by_order(keep, order, 5).tolist() == [7, 2, 7, 3, 0]
+    assert VO.select_by_order(keep, order, 3).tolist() == [7, 2, 7] and VO.cut_position(keep, order, 3) == 6
+    assert VO.select_by_order(keep, order, 6).tolist() == [0, 2, 3, 5, 6, 7]  # at most max_points kept: row-major, order unused
+
+
+def test_non_finite_vectors_are_dropped_by_the_oracle(gold):
+    c = VO.CASES["a"]
+    kw = dict(step=c["step"], min_mag=c["min_mag"], max_points=c["max_points"], grid_size=c["grid_size"], min_pairs=c["min_pairs"])
+    r = VO.estimate(gold["vec/a"], c["frame"], **kw)
+    cells = np.flatnonzero(r["keep"])
+    bad, zeroed = gold["vec/a"].copy(), gold["vec/a"].copy()
+    bad.reshape(-1, 2)[cells[3]] = np.nan
+    bad.reshape(-1, 2)[cells[10]] = (np.inf, 1.0)
+    zeroed.reshape(-1, 2)[cells[[3, 10]]] = 0.0
+    rb, rz = VO.estimate(bad, c["frame"], **kw), VO.estimate(zeroed, c["frame"], **kw)
+    assert rb["n_kept"] == rz["n_kept"] == r["n_kept"] - 2 and np.array_equal(rb["keep"], rz["keep"])
+    assert rb["status"] == rz["status"] == 0 and rb["xy"] == rz["xy"] and rb["prob"] == rz["prob"]
