@@ -490,9 +490,20 @@ int pwc_flow_upsample_f32(const void *flow_q, void *out, int n, int Hq, int Wq, 
  * pwc_pil_resize_planes_f32: src float [n][c][in_h][in_w] (dense planes, free batch stride in elements) -> dst [n][c][out_h][out_w]
  *   (dense).  ss = 0.0; ss += (double)src[first + t] * w[t] in tap order, multiply and add separate; (float)ss; horizontal pass first
  *   with a float intermediate.  factors (device, float [c], may be NULL): dst = (float)ss * factors[channel] in float.
+ * Two rules of Image.resize sit above the passes.  (1) It takes no pass on an axis whose length does not change, and copies when
+ *   neither does.  pwc_pil_resize_planes_f32 does the same: with in_w == out_w its horizontal stage copies the sample, with
+ *   in_h == out_h its vertical stage does, so -0.0, infinities and NaN stay where they are (the identity table would make +0.0 of
+ *   -0.0 and NaN of an inf's or a NaN's neighbour).  pwc_pil_resize_frames_u8 applies the identity table, which is exact on bytes:
+ *   its coefficient is 2^22 and (2^21 + v * 2^22) >> 22 == v.  (2) It takes the VERTICAL pass first when H > 100 * W and h < H.
+ *   Both entry points (ops.pil_resize_frames, ops.pil_resize_planes) are single-order, horizontal first, whatever the sizes; a caller
+ *   that wants Pillow's result for such a source makes two calls, (H, W) -> (h, W) and then (h, W) -> (h, w), each of which is a
+ *   one-axis resize by rule (1), the bytes of the first going through out_u8.  opticalflow_amd/pil_resize.py (resize_frames,
+ *   resize_planes, resize_flow, FrameIngest, infer_resized) does that.
  * One launch each (a workgroup resamples the source rows of its 16 x 64 output tile horizontally into LDS and takes the vertical pass
- * from there); neither allocates nor synchronises.  Supported: I <= 8 * O on both axes (a downscale of at most 8, ksize <= 17; any upscale), sizes <= 2^20
- * (pwc_pil_resize_supported: 1 / 0; pwc_pil_resize_ksize: the ksize of one axis, PWC_EINVAL outside the range).
+ * from there); neither allocates nor synchronises.  Supported: I <= 8 * O on both axes (a downscale of at most 8, ksize <= 17; any upscale), sizes <= 2^20;
+ * beyond 8 only to an output shorter than a tile, as long as what a tile stages still fits: min(O, T) * ksize <= T * 17 coefficients
+ * and at most 144 source rows (T = 16) / 522 source columns (T = 64) under it, e.g. 16 -> 1 or 29 -> 3 but not 129 -> 16
+ * (pwc_pil_resize_supported: 1 / 0; pwc_pil_resize_ksize: the ksize of one axis, PWC_EINVAL when the pair is supported on neither axis).
  * PWC_EINVAL, nothing launched: a null pointer (out_u8 / factors may be NULL), non-positive sizes or out_group, an unsupported scale,
  * a ksize that disagrees with the sizes, a batch stride smaller than the tensor, n (frames) or n * c (planes) > 65535.  PWC_EALIGN,
  * nothing launched: out_f32 / src / dst / bounds / int32 coefficients / lut768 / factors not 4-byte, float64 coefficients not 8-byte aligned. */

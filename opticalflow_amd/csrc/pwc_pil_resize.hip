@@ -7,6 +7,13 @@
 //            the vertical pass on those bytes, then lut[c][byte] (ToTensor + Normalize as a 3 x 256 float table made with torch).
 //   planes : ss = 0.0; ss += (double)src[first + t] * w[t] in tap order (separate multiply and add: -ffp-contract=off), (float)ss;
 //            horizontal first with a float intermediate; an optional per-channel float factor after the second pass.
+// Image.resize takes no pass on an axis whose length does not change (and copies when neither does).  The planes kernel does the
+// same: with iw == ow its horizontal stage copies the source sample, with ih == oh its vertical stage copies the staged one (both
+// conditions hold for a whole launch, so the host picks one of four instantiations), so -0.0, infinities and NaN stay where they are -- the identity table (0 * left + 1 * x
+// on top of ss = 0.0) would turn -0.0 into +0.0 and spread an inf or a NaN to the neighbour as NaN.  The frames kernel needs no such
+// branch: the identity coefficient is exactly 2^22 and (2^21 + v * 2^22) >> 22 == v for every byte, so applying the table IS the copy.
+// Image.resize also takes the VERTICAL pass first when H > 100 * W and h < H.  The kernels here are single-order, horizontal first;
+// opticalflow_amd/pil_resize.py composes that regime from two launches, (H, W) -> (h, W) and (h, W) -> (h, w), each a one-axis resize.
 // One launch.  A workgroup owns a 16 x 64 output tile of one image: it resamples the source rows its tile needs (they follow from the
 // vertical bounds of the tile's first and last row) horizontally into LDS and takes the vertical pass from there.  Frames: the
 // source bytes of a batch of rows come in as aligned dwords with the lanes along x (the taps of neighbouring outputs overlap, and a
@@ -23,8 +30,8 @@ namespace {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kTH = 16, kTW = 64;          // output tile
-constexpr int kMaxScale = 8;               // supported: in <= 8 * out per axis (an upscale has 3-tap rows whatever its factor)
-constexpr int kMaxK = 2 * kMaxScale + 1;   // ksize at the largest downscale
+constexpr int kMaxScale = 8;               // supported: in <= 8 * out per axis (an upscale has 3-tap rows whatever its factor), see axis_fits
+constexpr int kMaxK = 2 * kMaxScale + 1;   // ksize at that downscale: a tile's table slice holds kTW (kTH) rows of it
 // staged rows of a tile: the centres of 16 output rows span 15 * scale <= 120 source rows, the support adds <= 8 on each side and the
 // two roundings of the bounds at most 1 more: 137
 constexpr int kMaxRows = 144;
@@ -160,6 +167,9 @@ pil_frames_kernel(const uint8_t *__restrict__ src, float *__restrict__ out, uint
     }
 }
 
+// kCopyX / kCopyY: the axis keeps its length (iw == ow / ih == oh), so Pillow takes no pass on it and the stage copies.  Compile-time,
+// so that the instantiation with both passes is the code it was before the copies existed.
+template <bool kCopyX, bool kCopyY>
 __global__ void __launch_bounds__(256)
 pil_planes_kernel(const float *__restrict__ src, float *__restrict__ dst, int C, int ih, int iw, int oh, int ow,
                   const int32_t *__restrict__ xb, const double *__restrict__ xk, int xks, const int32_t *__restrict__ yb,
@@ -185,7 +195,9 @@ pil_planes_kernel(const float *__restrict__ src, float *__restrict__ dst, int C,
     for (int it = tid; it < rows * kTW; it += 256) {
         const int r = it >> 6, xl = it & 63;
         float o = 0.f;
-        if (xl < tw) {
+        if (kCopyX) {                            // unchanged axis: Pillow takes no horizontal pass, the sample is copied
+            if (xl < tw) o = img[(int64_t)(r0 + r) * iw + x0 + xl];
+        } else if (xl < tw) {
             const int2 b = s_xb[xl];
             const float *p = img + (int64_t)(r0 + r) * iw + b.x;
             const double *k = s_xk + xl * xks;
@@ -202,21 +214,26 @@ pil_planes_kernel(const float *__restrict__ src, float *__restrict__ dst, int C,
     for (int it = tid; it < th * kTW; it += 256) {
         const int yl = it >> 6, xl = it & 63;
         if (xl >= tw) continue;
-        const int2 b = s_yb[yl];
-        const double *k = s_yk + yl * yks;
-        double ss = 0.0;
-        for (int t = 0; t < b.y; ++t) ss += (double)s_rows[min(b.x - r0 + t, rows_cap - 1) * kTW + xl] * k[t];
-        const float v = (float)ss;
+        float v;
+        if (kCopyY) {                            // unchanged axis: no vertical pass, output row y is staged row y - r0
+            v = s_rows[min(max(y0 + yl - r0, 0), rows_cap - 1) * kTW + xl];
+        } else {
+            const int2 b = s_yb[yl];
+            const double *k = s_yk + yl * yks;
+            double ss = 0.0;
+            for (int t = 0; t < b.y; ++t) ss += (double)s_rows[min(b.x - r0 + t, rows_cap - 1) * kTW + xl] * k[t];
+            v = (float)ss;
+        }
         o[(int64_t)yl * ow + xl] = factors ? v * fac : v;
     }
 }
 
-// ksize of Pillow's coefficient rows for one axis; 0 when the pair is outside the supported scale range
+// ksize of Pillow's coefficient rows for one axis, whatever the scale; 0 for sizes that are not positive or above 2^20
 int axis_ksize(int in, int out) {
     if (in <= 0 || out <= 0 || in > kMaxDim || out > kMaxDim) return 0;
-    if ((int64_t)in > (int64_t)kMaxScale * out) return 0;
     const double scale = (double)in / (double)out;
-    return 2 * (int)ceil(scale < 1.0 ? 1.0 : scale) + 1;
+    const double k = 2.0 * ceil(scale < 1.0 ? 1.0 : scale) + 1.0;
+    return k > (double)(1 << 22) ? 0 : (int)k;
 }
 
 // upper bound of the source samples under `tile` consecutive outputs of one axis: the first tap is >= c0 - support - 0.5, the end of
@@ -226,19 +243,28 @@ int span_bound(int in, int out, int tile) {
     const int64_t b = (int64_t)ceil((tile - 1) * scale) + 2 * (int64_t)ceil(scale < 1.0 ? 1.0 : scale) + 2;
     return (int)(b < in ? b : in);
 }
+constexpr int kMaxCols = (kTW - 1) * kMaxScale + 2 * kMaxScale + 2;          // source columns under a tile at the largest downscale
 static_assert((kTH - 1) * kMaxScale + 2 * kMaxScale + 2 <= kMaxRows, "a tile's staged rows fit the LDS budget at the largest downscale");
+
+// What the kernels stage per tile decides the range: the tile's slice of the coefficient table (`tile` rows of kMaxK entries) and the
+// source span under it (`max_span` samples).  Every in <= kMaxScale * out fits (ksize <= kMaxK and the spans above); so does a
+// stronger downscale to an output shorter than a tile whose few, longer coefficient rows and short source still fit, e.g. 16 -> 1.
+bool axis_fits(int in, int out, int tile, int max_span) {
+    const int ks = axis_ksize(in, out);
+    if (!ks) return false;
+    return (int64_t)(out < tile ? out : tile) * ks <= (int64_t)tile * kMaxK && span_bound(in, out, tile) <= max_span;
+}
 
 constexpr int kRawBudget = 8192;           // bytes of source rows staged at a time
 
 }  // namespace
 
 extern "C" int pwc_pil_resize_ksize(int in_size, int out_size) {
-    const int k = axis_ksize(in_size, out_size);
-    return k ? k : PWC_EINVAL;
+    return axis_fits(in_size, out_size, kTW, kMaxCols) ? axis_ksize(in_size, out_size) : PWC_EINVAL;
 }
 
 extern "C" int pwc_pil_resize_supported(int in_h, int in_w, int out_h, int out_w) {
-    return axis_ksize(in_h, out_h) > 0 && axis_ksize(in_w, out_w) > 0 && (out_h + kTH - 1) / kTH <= 65535;
+    return axis_fits(in_h, out_h, kTH, kMaxRows) && axis_fits(in_w, out_w, kTW, kMaxCols) && (out_h + kTH - 1) / kTH <= 65535;
 }
 
 extern "C" int pwc_pil_resize_frames_u8(const void *frames_u8, void *out_f32, void *out_u8, int n, int H, int W, int h, int w,
@@ -249,7 +275,7 @@ extern "C" int pwc_pil_resize_frames_u8(const void *frames_u8, void *out_f32, vo
         PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: null pointer");
     if (n <= 0 || H <= 0 || W <= 0 || h <= 0 || w <= 0 || out_group <= 0) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: bad shape");
     if (!pwc_pil_resize_supported(H, W, h, w))
-        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: %dx%d -> %dx%d is outside the supported scale range (downscale <= 8 per axis)", H, W, h, w);
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: %dx%d -> %dx%d is outside the supported scale range (downscale <= 8 per axis, more only to outputs shorter than a tile)", H, W, h, w);
     if (xksize != axis_ksize(W, w) || yksize != axis_ksize(H, h))
         PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_frames_u8: ksize (%d, %d) disagrees with the sizes (%d, %d expected)", xksize, yksize,
                  axis_ksize(W, w), axis_ksize(H, h));
@@ -277,7 +303,7 @@ extern "C" int pwc_pil_resize_planes_f32(const void *src, void *dst, int n, int 
     if (!src || !dst || !xbounds || !xcoef || !ybounds || !ycoef) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: null pointer");
     if (n <= 0 || c <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: bad shape");
     if (!pwc_pil_resize_supported(in_h, in_w, out_h, out_w))
-        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: %dx%d -> %dx%d is outside the supported scale range (downscale <= 8 per axis)", in_h, in_w,
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: %dx%d -> %dx%d is outside the supported scale range (downscale <= 8 per axis, more only to outputs shorter than a tile)", in_h, in_w,
                  out_h, out_w);
     if (xksize != axis_ksize(in_w, out_w) || yksize != axis_ksize(in_h, out_h))
         PWC_FAIL(PWC_EINVAL, "pwc_pil_resize_planes_f32: ksize (%d, %d) disagrees with the sizes (%d, %d expected)", xksize, yksize,
@@ -287,7 +313,10 @@ extern "C" int pwc_pil_resize_planes_f32(const void *src, void *dst, int n, int 
     if (pwc::misaligned({src, dst, xbounds, ybounds, factors}) || pwc::misaligned({xcoef, ycoef}, 8))
         PWC_FAIL(PWC_EALIGN, "pwc_pil_resize_planes_f32: planes / bounds must be 4-byte, coefficients 8-byte aligned");
     const int rows_cap = span_bound(in_h, out_h, kTH);
-    hipLaunchKernelGGL(pil_planes_kernel, dim3((out_w + kTW - 1) / kTW, (out_h + kTH - 1) / kTH, n * c), dim3(256),
+    const bool copy_x = in_w == out_w, copy_y = in_h == out_h;
+    const auto kernel = copy_x ? (copy_y ? pil_planes_kernel<true, true> : pil_planes_kernel<true, false>)
+                               : (copy_y ? pil_planes_kernel<false, true> : pil_planes_kernel<false, false>);
+    hipLaunchKernelGGL(kernel, dim3((out_w + kTW - 1) / kTW, (out_h + kTH - 1) / kTH, n * c), dim3(256),
                        rows_cap * kTW * sizeof(float), static_cast<hipStream_t>(stream), static_cast<const float *>(src),
                        static_cast<float *>(dst), c, in_h, in_w, out_h, out_w, xbounds, xcoef, xksize, ybounds, ycoef, yksize, factors,
                        src_bstride, rows_cap);

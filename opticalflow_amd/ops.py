@@ -496,7 +496,8 @@ def flow_upsample(flow_q: torch.Tensor, crop_h: int, crop_w: int, out_h: int, ou
 
 
 def pil_resize_supported(in_hw, out_hw) -> bool:
-    """True when the Pillow-exact resize kernels take this geometry: scale factors 1/8 .. 8 on both axes (there is no fallback)."""
+    """True when the Pillow-exact resize kernels take this geometry: any upscale and a downscale of at most 8 per axis, more only to
+    an output shorter than a tile (16 rows, 64 columns) whose coefficient rows and source span still fit one (there is no fallback)."""
     (ih, iw), (oh, ow) = in_hw, out_hw
     if min(ih, iw, oh, ow) <= 0 or max(ih, iw, oh, ow) >= 2 ** 31:
         return False

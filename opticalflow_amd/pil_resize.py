@@ -5,7 +5,12 @@ The coefficient tables are made here on the host (`coeff_tables`, `fixed_point`:
 the C cast, so they are Pillow's), uploaded once per (input length, output length, device) and kept; the kernels of
 csrc/pwc_pil_resize.hip only apply them.  Once the tables of a geometry are resident, `resize_frames` / `resize_flow` neither
 allocate tables nor synchronise and can be captured in a HIP graph.  There is no CPU fallback: outside the supported scale range
-(ops.pil_resize_supported) the calls raise."""
+(ops.pil_resize_supported) the calls raise.
+
+Two rules of Image.resize sit above its two passes.  It takes no pass on an axis whose length does not change: the planes kernel
+copies there (the frames kernel's identity table is exact on bytes).  And it takes the vertical pass first when the source is more
+than 100 times as tall as wide and its height shrinks (`vertical_first`): the kernels are horizontal-first, so that regime is
+composed here from two launches, (H, W) -> (h, W) and (h, W) -> (h, w), each a one-axis resize."""
 from __future__ import annotations
 
 import math
@@ -111,15 +116,29 @@ def _size(size) -> Tuple[int, int]:
 def _check_supported(in_hw, out_hw) -> None:
     from . import ops
     if not ops.pil_resize_supported(in_hw, out_hw):
-        raise ValueError("resize %dx%d -> %dx%d is outside the supported range (a downscale of at most 8 per axis); there is no "
-                         "fallback" % (in_hw[0], in_hw[1], out_hw[0], out_hw[1]))
+        raise ValueError("resize %dx%d -> %dx%d is outside the supported range (a downscale of at most 8 per axis, more only to an "
+                         "output shorter than a tile); there is no fallback" % (in_hw[0], in_hw[1], out_hw[0], out_hw[1]))
+
+
+def vertical_first(in_hw, out_hw) -> bool:
+    """Image.resize's pass order (the end of PIL/Image.py's resize): the vertical pass first when H > 100 * W and h < H."""
+    return in_hw[0] > 100 * in_hw[1] and out_hw[0] < in_hw[0]
+
+
+def _steps(in_hw, out_hw):
+    """The launches of one resize as (source size, target size): one, or for a tall source the vertical pass and then the horizontal."""
+    if vertical_first(in_hw, out_hw):
+        mid = (out_hw[0], in_hw[1])
+        return ((tuple(in_hw), mid), (mid, tuple(out_hw)))
+    return ((tuple(in_hw), tuple(out_hw)),)
 
 
 def prepare(in_hw, out_hw, device, frames: bool = True, mean=None, std=None) -> None:
     """Make the tables of one geometry resident (what the first call does), e.g. before capturing a graph."""
     _check_supported(in_hw, out_hw)
-    _axis_tables(in_hw[1], out_hw[1], frames, device)
-    _axis_tables(in_hw[0], out_hw[0], frames, device)
+    for src, dst in _steps(in_hw, out_hw):
+        _axis_tables(src[1], dst[1], frames, device)
+        _axis_tables(src[0], dst[0], frames, device)
     if frames:
         _lut(mean, std, device)
 
@@ -130,9 +149,16 @@ def _resize_frames(frames_u8: torch.Tensor, size, mean, std, out: torch.Tensor, 
     n, H, W, _ = frames_u8.shape
     h, w = size
     _check_supported((H, W), (h, w))
-    xt = _axis_tables(W, w, True, frames_u8.device)
-    yt = _axis_tables(H, h, True, frames_u8.device)
-    return ops.pil_resize_frames(frames_u8, (h, w), xt, yt, _lut(mean, std, frames_u8.device), out, out_u8, group)
+    dev = frames_u8.device
+    if vertical_first((H, W), (h, w)):
+        # Pillow's order for a tall source: the vertical pass alone, its bytes kept (the float planes of this launch are not used)
+        mid = torch.empty((n, h, W, 3), dtype=torch.uint8, device=dev)
+        ops.pil_resize_frames(frames_u8, (h, W), _axis_tables(W, W, True, dev), _axis_tables(H, h, True, dev), _lut(mean, std, dev),
+                              torch.empty((n, 3, h, W), dtype=torch.float32, device=dev), mid, n)
+        frames_u8, H = mid, h
+    xt = _axis_tables(W, w, True, dev)
+    yt = _axis_tables(H, h, True, dev)
+    return ops.pil_resize_frames(frames_u8, (h, w), xt, yt, _lut(mean, std, dev), out, out_u8, group)
 
 
 def resize_frames(frames_u8: torch.Tensor, size, mean=None, std=None, out: Optional[torch.Tensor] = None, return_u8: bool = False):
@@ -159,6 +185,9 @@ def resize_planes(x: torch.Tensor, size, factors: Optional[Sequence[float]] = No
     H, W = _size(size)
     n, c, h, w = x.shape
     _check_supported((h, w), (H, W))
+    if vertical_first((h, w), (H, W)):          # Pillow's order for a tall source: the vertical pass alone, then the horizontal one
+        x = ops.pil_resize_planes(x, (H, w), _axis_tables(w, w, False, x.device), _axis_tables(h, H, False, x.device))
+        h = H
     xt = _axis_tables(w, W, False, x.device)
     yt = _axis_tables(h, H, False, x.device)
     fac = None

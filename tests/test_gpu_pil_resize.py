@@ -81,18 +81,19 @@ def test_two_runs_give_the_same_bits(gpu_device):
 
 
 def test_out_of_range_scale_raises(gpu_device):
-    frames = torch.zeros((1, 72, 8, 3), dtype=torch.uint8, device=gpu_device)
-    assert ops.pil_resize_supported((64, 8), (8, 8)) and not ops.pil_resize_supported((72, 8), (8, 8))
+    # 129 -> 16 is the first length past a downscale of 8 whose 16 rows of coefficients (ksize 19) no longer fit a tile's slice
+    frames = torch.zeros((1, 129, 8, 3), dtype=torch.uint8, device=gpu_device)
+    assert ops.pil_resize_supported((128, 8), (16, 8)) and not ops.pil_resize_supported((129, 8), (16, 8))
     with pytest.raises(ValueError, match="supported range"):
-        pil_resize.resize_frames(frames, (8, 8))
+        pil_resize.resize_frames(frames, (16, 8))
     with pytest.raises(ValueError, match="supported range"):
-        pil_resize.resize_flow(torch.zeros((1, 2, 4, 33), device=gpu_device), (4, 4))
+        pil_resize.resize_flow(torch.zeros((1, 2, 4, 513), device=gpu_device), (4, 64))
     # the library refuses it too when the wrapper's check is bypassed
     xt = pil_resize._axis_tables(8, 8, True, gpu_device)
-    yt = pil_resize._axis_tables(72, 8, True, gpu_device)
-    out = torch.empty((1, 3, 8, 8), device=gpu_device)
+    yt = pil_resize._axis_tables(129, 16, True, gpu_device)
+    out = torch.empty((1, 3, 16, 8), device=gpu_device)
     with pytest.raises(ops.PwcHipError, match="supported"):
-        ops.pil_resize_frames(frames, (8, 8), xt, yt, pil_resize._lut(None, None, gpu_device), out)
+        ops.pil_resize_frames(frames, (16, 8), xt, yt, pil_resize._lut(None, None, gpu_device), out)
 
 
 def test_frame_ingest_pairs_equal_per_frame_resize(gpu_device):

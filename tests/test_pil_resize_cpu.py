@@ -75,7 +75,9 @@ def test_oracle_equals_live_pillow_sweep():
 
 # ------------------------------------------------------------------ 3. table facts
 @pytest.mark.parametrize("I,O", [(1080, 384), (1920, 512), (375, 384), (94, 96), (5, 64), (1, 8), (512, 64), (520, 65), (64, 512),
-                                 (201, 67), (40, 7), (33, 1)])
+                                 (201, 67), (40, 7), (33, 1),
+                                 # the edge cases of g20 (tests/test_pil_resize_edges_cpu.py)
+                                 (263, 33), (1037, 130), (648, 130), (3, 40), (5, 200), (2, 130), (300, 70), (1, 20), (9, 2)])
 def test_coeff_tables_facts(I, O):
     bounds, coeffs = pil_resize.coeff_tables(I, O)
     ks = pil_resize.ksize(I, O)
@@ -185,7 +187,11 @@ def test_supported_predicates():
     lib = _lib.load()
     for I, O in ((1080, 384), (1920, 512), (375, 384), (64, 512), (512, 64), (1, 8), (8, 1), (520, 65), (96, 375), (5, 64), (1, 9), (64, 513)):
         assert lib.pwc_pil_resize_ksize(I, O) == pil_resize.ksize(I, O)
-    for I, O in ((513, 64), (9, 1), (0, 4), (4, 0), (-1, 4), ((1 << 20) + 1, 1 << 20)):
+    # more than 8 only to an output shorter than a tile, while the tile's table slice (64 rows of 17 entries on x) and its source
+    # span still fit what the kernels stage: 9 -> 1 (ksize 21), 16 -> 1 (33), 29 -> 3 (21), 512 -> 32 (33 x 32 = 1056 entries)
+    for I, O in ((9, 1), (16, 1), (29, 3), (512, 32), (72, 8)):
+        assert lib.pwc_pil_resize_ksize(I, O) == pil_resize.ksize(I, O) > 17
+    for I, O in ((513, 64), (1041, 130), (545, 33), (2000, 3), (0, 4), (4, 0), (-1, 4), ((1 << 20) + 1, 1 << 20)):
         assert lib.pwc_pil_resize_ksize(I, O) == -1
     assert ops.pil_resize_supported((1080, 1920), (384, 512)) and ops.pil_resize_supported((375, 1242), (384, 1280))
     assert ops.pil_resize_supported((96, 320), (375, 1242)) and ops.pil_resize_supported((512, 520), (64, 65))
@@ -193,6 +199,11 @@ def test_supported_predicates():
     assert not ops.pil_resize_supported((513, 64), (64, 64)) and not ops.pil_resize_supported((64, 513), (64, 64))
     assert ops.pil_resize_supported((64, 64), (513, 64)) and ops.pil_resize_supported((129, 5), (64, 64))          # any upscale
     assert not ops.pil_resize_supported((0, 64), (64, 64)) and not ops.pil_resize_supported((64, 64), (64, -2))
+    # the short-output extension is per axis and per tile: 16 rows of 17 entries on y, 64 rows on x
+    assert ops.pil_resize_supported((16, 16), (1, 1)) and ops.pil_resize_supported((9, 9), (1, 1)) and ops.pil_resize_supported((37, 29), (19, 3))
+    assert ops.pil_resize_supported((128, 8), (16, 8)) and not ops.pil_resize_supported((129, 8), (16, 8)) and ops.pil_resize_supported((8, 129), (8, 16))
+    assert ops.pil_resize_supported((126, 8), (14, 8)) and not ops.pil_resize_supported((127, 8), (14, 8))          # 14 x 19 <= 16 x 17 < 14 x 21
+    assert not ops.pil_resize_supported((4, 513), (4, 64)) and not ops.pil_resize_supported((2000, 4), (3, 4))
     with pytest.raises(ValueError, match="supported range"):
         pil_resize.prepare((2160, 3840), (64, 64), "cpu")
     with pytest.raises(ValueError):
