@@ -516,6 +516,40 @@ int pwc_pil_resize_planes_f32(const void *src, void *dst, int n, int c, int in_h
                               const int32_t *xbounds, const double *xcoef, int xksize, const int32_t *ybounds, const double *ycoef,
                               int yksize, const float *factors, int64_t src_bstride, void *stream);
 
+/* cv2.resize-exact INTER_LINEAR resize (ABI v13 additions, csrc/pwc_cv_resize.hip): the two cv2.resize calls around the model in
+ * script_pwc.py:43-83 and topview.py:79-119 (compute_flow), with what surrounds them -- channel flip, / 255, HWC -> CHW, stacking on
+ * the way in; the gain (x 20 in script_pwc.py), the resize and the u / v rescale on the way out.  "Exact" means equal to this project's
+ * statement of OpenCV's published algorithm (opticalflow_amd/harness.py, pinned by tests/test_harness.py); cv2 parity unpinned.  Per
+ * axis with input length I and output length O the HOST makes (opticalflow_amd/cv_resize.py axis_table):
+ *   scale = 1.0 / ((double)O / (double)I); for each output index d: fx = (float)((d + 0.5) * scale - 0.5); s0 = floor(fx); fx -= s0;
+ *   s0 < 0 -> (0, fx = 0); s0 >= I - 1 -> (I - 1, fx = 0).
+ * xs0 / ys0 are int32 [O] (first tap), xfx / yfy float [O] (weight of the second tap, s1 = min(s0 + 1, I - 1)).  All tables are DEVICE
+ * pointers; the kernels clamp s0 into [0, I), so no tap leaves the image whatever a table holds.
+ * pwc_cv_resize_frames_u8: frames uint8 [n][H][W][3] (interleaved, dense) -> out_f32 planes of [h][w].  a0 = cvRound((1.f - fx) * 2048),
+ *   a1 = cvRound(fx * 2048) (round half to even, each on its own: their sum may be 2047 or 2049), b0 / b1 alike from fy;
+ *   D = S[s0] * a0 + S[s1] * a1 in int32 on source rows y0 and y1; byte = (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2;
+ *   out_f32 = lut768[c_out * 256 + byte] with c_out = flip_channels ? 2 - c : c (float [3][256], device: / 255 and any normalisation
+ *   tabulated by the caller, indexed by the OUTPUT channel).  Frame f is written to
+ *   out_f32 + (f % out_group) * out_bstride + (f / out_group) * 3 * h * w (elements), as pwc_pil_resize_frames_u8 does: out_group = n
+ *   gives [n][3][h][w] with a free batch stride; pairs [n][2][H][W][3] taken as 2n frames with out_group = 2n and
+ *   out_bstride = 3 * h * w fill a dense [n][6][h][w] network input in one launch.  H == h && W == w needs no special case: weight 2048 is
+ *   exact on bytes.
+ * pwc_cv_resize_flow_f32: src float [n][2][in_h][in_w] (dense planes, free batch stride in elements) -> dst [n][2][out_h][out_w], or
+ *   [n][out_h][out_w][2] when hwc (dense).  In float32, every product and sum rounded (no fused multiply-add): t = src * gain;
+ *   row = t[s0] * (1.f - fx) + t[s1] * fx; val = row[y0] * (1.f - fy) + row[y1] * fy; dst = val * (channel 0 ? fu : fv).  When both sizes
+ *   are equal cv2 copies: dst = (src * gain) * f, so -0.0, infinities and NaN stay where they are.
+ * One launch each, a direct four-tap gather: a thread owns four consecutive outputs of a row in every channel and stores 16 bytes per
+ * plane where out_w % 4 == 0 and the output is 16-byte aligned (frames: out_bstride % 4 == 0 too), single floats otherwise.  Neither
+ * allocates nor synchronises; both can be captured in a graph.
+ * PWC_EINVAL, nothing launched: a null pointer, a size outside 1..2^20, non-positive n or out_group, a batch stride smaller than the
+ * tensor, n > 65535.  PWC_EALIGN, nothing launched: out_f32 / src / dst / a table not 4-byte aligned. */
+int pwc_cv_resize_frames_u8(const void *frames_u8, void *out_f32, int n, int H, int W, int h, int w, const int32_t *xs0,
+                            const float *xfx, const int32_t *ys0, const float *yfy, const float *lut768, int flip_channels,
+                            int64_t out_bstride, int out_group, void *stream);
+int pwc_cv_resize_flow_f32(const void *src, void *dst, int n, int in_h, int in_w, int out_h, int out_w, const int32_t *xs0,
+                           const float *xfx, const int32_t *ys0, const float *yfy, float gain, float fu, float fv, int hwc,
+                           int64_t src_bstride, void *stream);
+
 /* KITTI scoring on the device (ABI v13 additions, csrc/pwc_kitti_score.hip): EPE and Fl-all of inference_kitti.py:94-128
  * (epe_metric / fl_all_metric) straight from the network's quarter-resolution flow, nothing image-sized written unless asked for.
  * flow_q [n][2][Hq][Wq] f32 (dense planes, batch stride in elements).  Per pixel (b, y, x) of the out_h x out_w grid, in fp32 with

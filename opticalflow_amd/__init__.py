@@ -15,6 +15,8 @@ from . import augment_full  # noqa: F401
 from .augment_full import DeviceFullAugmenter, augment_full_batch  # noqa: F401
 from . import pil_resize  # noqa: F401
 from .pil_resize import resize_flow, resize_frames  # noqa: F401
+from . import cv_resize  # noqa: F401
+from .cv_resize import CvGraphedInfer  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import FusedAdam, FusedAdamW  # noqa: F401
 from . import compare  # noqa: F401

@@ -20,7 +20,7 @@ restatement is pinned by hand-computed known-answer vectors and an independent s
 (tests/test_harness.py), not against cv2: "parity unpinned" w.r.t. an actual cv2 build (whose SIMD / IPP variants
 are documented to match the scalar code above).
 
-CLI:  python -m opticalflow_amd.harness im1.png im2.png out.flo [--weights pwc_net.pth.tar] [--png out.png]
+CLI:  python -m opticalflow_amd.harness im1.png im2.png out.flo [--weights pwc_net.pth.tar] [--png out.png] [--prepost {torch,hip}]
 """
 from __future__ import annotations
 
@@ -117,9 +117,21 @@ def postprocess(flow2: torch.Tensor, h: int, w: int) -> torch.Tensor:
 
 
 @torch.no_grad()
-def estimate_flow(net, im1: torch.Tensor, im2: torch.Tensor) -> torch.Tensor:
-    """Full script_pwc.py pipeline for one pair; images may live on the host (moved to the net's device)."""
+def estimate_flow(net, im1: torch.Tensor, im2: torch.Tensor, prepost: str = "torch") -> torch.Tensor:
+    """Full script_pwc.py pipeline for one pair; images may live on the host (moved to the net's device).  prepost="hip": uint8
+    images go through the two kernels of opticalflow_amd.cv_resize (the same resize arithmetic, and the reference's IEEE division by
+    255 where the torch chain multiplies by the reciprocal); float images keep the torch chain."""
+    if prepost not in ("torch", "hip"):
+        raise ValueError("prepost must be 'torch' or 'hip', got %r" % (prepost,))
     dev = next(net.parameters()).device
+    if prepost == "hip" and im1.dtype == torch.uint8 and im2.dtype == torch.uint8:
+        from . import cv_resize
+        if im1.shape[:2] != im2.shape[:2]:
+            raise ValueError("image sizes differ: %s vs %s" % (tuple(im1.shape), tuple(im2.shape)))
+        pair = torch.stack((im1[:, :, :3].to(dev), im2[:, :, :3].to(dev))).unsqueeze(0)          # drop alpha -> [1,2,H,W,3]
+        out = net(cv_resize.ingest_pairs(pair))
+        flow2 = out[0] if isinstance(out, (tuple, list)) else out
+        return cv_resize.resize_flow(flow2, im1.shape[:2], gain=20.0, layout="hwc")[0]
     x = preprocess(im1.to(dev), im2.to(dev))
     return postprocess(net(x), im1.shape[0], im1.shape[1])
 
@@ -147,11 +159,13 @@ def main(argv=None) -> int:
                     help="warp with grid_sample(align_corners=True) (torch < 1.3 behaviour, what the published weights saw)")
     ap.add_argument("--png", default=None, metavar="PATH",
                     help="also write the colour-wheel image of the flow (pwc_extract_flow.py's flow_to_color), made on the device")
+    ap.add_argument("--prepost", choices=("torch", "hip"), default="torch",
+                    help="image-space steps as the torch-op chain (default) or as the two cv_resize kernels")
     args = ap.parse_args(argv)
     from .pwcnet import pwc_dc_net
     net = pwc_dc_net(args.weights, normalize_corr=not args.cpu_fallback_semantics, align_corners=args.align_corners)
     net = net.cuda().eval()
-    flo = estimate_flow(net, read_image(args.im1), read_image(args.im2))
+    flo = estimate_flow(net, read_image(args.im1), read_image(args.im2), prepost=args.prepost)
     write_flo(args.out, flo.cpu())
     if args.png:
         from .flowio import write_png8_rgb

@@ -564,6 +564,68 @@ def pil_resize_planes(x: torch.Tensor, size: Tuple[int, int], xtab, ytab, factor
     return out
 
 
+def _cv_axis_arg(tab, out_size: int, device, name: str) -> Tuple[int, int]:
+    """(first taps int32 [O], weights float32 [O]) of one axis as cv_resize.axis_table makes them, on the device -> their pointers."""
+    s0, fx = tab
+    for t in (s0, fx):
+        if not torch.is_tensor(t) or not t.is_cuda:
+            raise ValueError("%s axis table must be device tensors" % name)
+    return (_table_arg(s0, torch.int32, out_size, device, name + " first taps"),
+            _table_arg(fx, torch.float32, out_size, device, name + " weights"))
+
+
+def cv_resize_frames(frames_u8: torch.Tensor, size: Tuple[int, int], xtab, ytab, lut: torch.Tensor, out: torch.Tensor,
+                     flip_channels: bool = True, group: Optional[int] = None) -> torch.Tensor:
+    """uint8 frames [n,H,W,3] -> out float32 [group, 3*ceil(n/group), h, w] (dense planes, free batch stride): cv2.resize's INTER_LINEAR
+    in its 11-bit fixed point, the channel order flipped when asked, then lut[c_out][byte] (C-ABI pwc_cv_resize_frames_u8).  xtab /
+    ytab: (first taps int32 [O], weights float32 [O]) on the device; lut float32 [3,256] on the device, indexed by the output channel."""
+    if not torch.is_tensor(frames_u8) or not frames_u8.is_cuda or frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 \
+            or frames_u8.shape[3] != 3 or not frames_u8.is_contiguous():
+        raise ValueError("frames_u8 must be a contiguous uint8 device tensor [n,H,W,3]")
+    n, H, W, _ = frames_u8.shape
+    h, w = (int(v) for v in size)
+    group = n if group is None else int(group)
+    dev = frames_u8.device
+    if group <= 0 or min(n, H, W, h, w) <= 0:
+        raise ValueError("group and every size must be positive")
+    want = (min(group, n), 3 * ((n + group - 1) // group), h, w)
+    if not torch.is_tensor(out) or out.dtype != torch.float32 or out.device != dev or tuple(out.shape) != want:
+        raise ValueError("out must be float32 %s on %s" % (want, dev))
+    if not torch.is_tensor(lut) or not lut.is_cuda:
+        raise ValueError("lut must be a float32 device tensor [3,256]")
+    bso = _plane_dense(out, "out")
+    xs, xf = _cv_axis_arg(xtab, w, dev, "x")
+    ys, yf = _cv_axis_arg(ytab, h, dev, "y")
+    lp = _table_arg(lut, torch.float32, 768, dev, "lut")
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_cv_resize_frames_u8(frames_u8.data_ptr(), out.data_ptr(), n, H, W, h, w, xs, xf, ys, yf, lp,
+                                                 1 if flip_channels else 0, bso, group, _stream(frames_u8))
+    check(rc, "pwc_cv_resize_frames_u8")
+    return out
+
+
+def cv_resize_flow(flow: torch.Tensor, size: Tuple[int, int], xtab, ytab, gain: float = 1.0, fu: float = 1.0, fv: float = 1.0,
+                   hwc: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 flow [n,2,h,w] (dense planes, free batch stride) -> [n,2,H,W], or [n,H,W,2] with hwc: (flow * gain) resized as cv2.resize
+    does float images (INTER_LINEAR, float32 passes), channel 0 times fu and channel 1 times fv (C-ABI pwc_cv_resize_flow_f32).
+    xtab / ytab: (first taps int32 [O], weights float32 [O]) on the device."""
+    if not torch.is_tensor(flow) or not flow.is_cuda or flow.dtype != torch.float32 or flow.dim() != 4 or flow.shape[1] != 2:
+        raise ValueError("flow must be a float32 device tensor [n,2,h,w]")
+    n, _, h, w = flow.shape
+    H, W = (int(v) for v in size)
+    if min(n, h, w, H, W) <= 0:
+        raise ValueError("every size must be positive")
+    bss = _plane_dense(flow, "flow")
+    out = _out_arg(out, (n, H, W, 2) if hwc else (n, 2, H, W), torch.float32, flow.device, contiguous=True)
+    xs, xf = _cv_axis_arg(xtab, W, flow.device, "x")
+    ys, yf = _cv_axis_arg(ytab, H, flow.device, "y")
+    with torch.cuda.device(flow.device):
+        rc = _lib.load().pwc_cv_resize_flow_f32(flow.data_ptr(), out.data_ptr(), n, h, w, H, W, xs, xf, ys, yf, float(gain), float(fu),
+                                                float(fv), 1 if hwc else 0, bss, _stream(flow))
+    check(rc, "pwc_cv_resize_flow_f32")
+    return out
+
+
 def kitti_score_workspace_bytes(n: int, out_h: int, out_w: int) -> int:
     return _query_bytes(_lib.load().pwc_kitti_score_workspace_bytes(n, out_h, out_w), "kitti-score")
 
