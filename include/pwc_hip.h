@@ -550,6 +550,33 @@ int pwc_cv_resize_flow_f32(const void *src, void *dst, int n, int in_h, int in_w
                            const float *xfx, const int32_t *ys0, const float *yfy, float gain, float fu, float fv, int hwc,
                            int64_t src_bstride, void *stream);
 
+/* cv2.warpPerspective-exact warp of 8-bit frames (ABI v13 addition, csrc/pwc_cv_warp.hip): the cv2.warpPerspective(frame, M,
+ * (width, height)) of topview.py:218,232 with the script's defaults INTER_LINEAR, BORDER_CONSTANT, border value 0.  "Exact" means
+ * equal to this project's statement of OpenCV's published algorithm (imgproc's warpPerspective plus the 8-bit bilinear remap; as
+ * NumPy in tests/cv_warp_oracle.py); cv2 parity unpinned.  Also unpinned: how OpenCV's int16 weight table stores the single weight
+ * 32768 at ax = ay = 0; it is taken as 32768, so an identity warp returns the image.
+ * src uint8 [n][H][W][3], dst uint8 [n][h][w][3], both dense frames with free batch strides in BYTES.  mat9: DEVICE pointer to the
+ * INVERSE map Mi (destination -> source), 9 doubles row-major per frame; frame f uses mat9 + f * mat_stride (0: one matrix for all
+ * frames, 9: one each).  The host inverts (opticalflow_amd/cv_warp.py invert3x3: OpenCV's closed 3x3 form, determinant by cofactor
+ * expansion along the first row, d = 1.0 / det, each adjugate entry times d).
+ * Coordinates, float64, every product and sum rounded separately (no fused multiply-add), for destination pixel (x, y):
+ *   bh0 = min(16, h); bw0 = min(1024 / bh0, w); xb = (x / bw0) * bw0; x1 = x - xb   (OpenCV's block origin and offset; integer)
+ *   X0 = (Mi[0]*xb + Mi[1]*y) + Mi[2];  Y0 = (Mi[3]*xb + Mi[4]*y) + Mi[5];  W0 = (Mi[6]*xb + Mi[7]*y) + Mi[8]
+ *   Wd = W0 + Mi[6]*x1;  Wd = (Wd != 0) ? 32.0 / Wd : 0.0                           (IEEE double division)
+ *   fX = max(-2147483648.0, min(2147483647.0, (X0 + Mi[0]*x1) * Wd));  fY alike with Y0 and Mi[3]
+ *        (std::min / std::max as OpenCV writes them: a NaN product becomes 2147483647.0)
+ *   X = cvRound(fX) (round half to even, int32);  sx = clamp(X >> 5, -32768, 32767) (arithmetic shift);  ax = X & 31;  Y, sy, ay alike
+ * Pixel, integer: over the four taps (sx + dx, sy + dy), dx, dy in {0, 1}, with wx in {32 - ax, ax} and wy in {32 - ay, ay}, a tap
+ * outside [0, W) x [0, H) contributing 0: per channel D = (sum wx * wy * S_tap + 512) >> 10.  This is OpenCV's 15-bit table form
+ * (sum w15 * S + 16384) >> 15 with w15 = 32 * wx * wy, exact for bilinear weights at 1 / 32 steps.
+ * One launch for the n frames, a direct gather: a thread owns four consecutive destination pixels of one row and stores them as three
+ * dwords where w % 4 == 0 and dst and dst_bstride are 4-byte aligned, as bytes otherwise.  No tap address leaves its frame.  Neither
+ * allocates nor synchronises; can be captured in a graph.
+ * PWC_EINVAL, nothing launched: a null pointer, a size outside 1..32767 (the statement's int16 coordinate range), n outside 1..65535,
+ * mat_stride not 0 or 9, a batch stride smaller than its frame.  PWC_EALIGN, nothing launched: mat9 not 8-byte aligned. */
+int pwc_cv_warp_perspective_u8(const void *src_u8, void *dst_u8, int n, int H, int W, int h, int w, const double *mat9, int mat_stride,
+                               int64_t src_bstride, int64_t dst_bstride, void *stream);
+
 /* KITTI scoring on the device (ABI v13 additions, csrc/pwc_kitti_score.hip): EPE and Fl-all of inference_kitti.py:94-128
  * (epe_metric / fl_all_metric) straight from the network's quarter-resolution flow, nothing image-sized written unless asked for.
  * flow_q [n][2][Hq][Wq] f32 (dense planes, batch stride in elements).  Per pixel (b, y, x) of the out_h x out_w grid, in fp32 with

@@ -17,6 +17,8 @@ from . import pil_resize  # noqa: F401
 from .pil_resize import resize_flow, resize_frames  # noqa: F401
 from . import cv_resize  # noqa: F401
 from .cv_resize import CvGraphedInfer  # noqa: F401
+from . import cv_warp  # noqa: F401
+from .cv_warp import TopviewInfer, TopviewStream  # noqa: F401
 from . import optim  # noqa: F401
 from .optim import FusedAdam, FusedAdamW  # noqa: F401
 from . import compare  # noqa: F401

@@ -41,6 +41,19 @@ def _plane_dense(t: torch.Tensor, name: str) -> int:
     return sb
 
 
+def _frames_dense(t: torch.Tensor, name: str) -> int:
+    """uint8 device frames [n,H,W,3] with dense [H,W,3] frames -> the batch stride in bytes (free, e.g. one half of a pair buffer)."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.uint8 or t.dim() != 4 or t.shape[3] != 3:
+        raise ValueError("%s must be a uint8 device tensor [n,H,W,3]" % name)
+    n, H, W, _ = t.shape
+    if min(n, H, W) <= 0:
+        raise ValueError("%s: every size must be positive" % name)
+    sb, sh, sw, sc = t.stride()
+    if sc != 1 or (W > 1 and sw != 3) or (H > 1 and sh != 3 * W) or (n > 1 and sb < 3 * H * W):
+        raise ValueError("%s must have dense [H,W,3] frames (strides %s for shape %s)" % (name, t.stride(), tuple(t.shape)))
+    return sb if n > 1 else 3 * H * W
+
+
 def densify(t: torch.Tensor) -> torch.Tensor:
     """Return t if its C,H,W planes are dense (batch stride free), else a contiguous copy."""
     if t.dim() == 4:

@@ -16,7 +16,7 @@ from typing import Optional, Tuple
 import torch
 
 from . import _lib
-from ._args import (_bias_arg, _dtype_code, _f32_dense, _kitti_gt_arg, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr,
+from ._args import (_bias_arg, _dtype_code, _f32_dense, _frames_dense, _kitti_gt_arg, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr,
                     _query_bytes, _require_device, _scalar_arg, _scratch, _stream, _table_arg, _workspace_args, densify)
 from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F32, PwcHipError, check)
 
@@ -623,6 +623,27 @@ def cv_resize_flow(flow: torch.Tensor, size: Tuple[int, int], xtab, ytab, gain: 
         rc = _lib.load().pwc_cv_resize_flow_f32(flow.data_ptr(), out.data_ptr(), n, h, w, H, W, xs, xf, ys, yf, float(gain), float(fu),
                                                 float(fv), 1 if hwc else 0, bss, _stream(flow))
     check(rc, "pwc_cv_resize_flow_f32")
+    return out
+
+
+def cv_warp_perspective(frames_u8: torch.Tensor, mats: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+    """uint8 frames [n,H,W,3] -> out uint8 [n,h,w,3] (both dense frames, free batch strides): cv2.warpPerspective's INTER_LINEAR /
+    BORDER_CONSTANT 0 with the INVERSE maps `mats`, float64 [9] (one for all frames) or [n,9] on the device (C-ABI
+    pwc_cv_warp_perspective_u8)."""
+    sbs = _frames_dense(frames_u8, "frames_u8")
+    dbs = _frames_dense(out, "out")
+    n, H, W, _ = frames_u8.shape
+    dev = frames_u8.device
+    if out.shape[0] != n or out.device != dev:
+        raise ValueError("out must hold %d frames on %s" % (n, dev))
+    h, w = out.shape[1:3]
+    if not torch.is_tensor(mats) or mats.dim() not in (1, 2) or mats.shape[-1] != 9 or (mats.dim() == 2 and mats.shape[0] != n):
+        raise ValueError("mats must be float64 [9] or [%d,9]" % n)
+    mp = _table_arg(mats, torch.float64, 9 * (n if mats.dim() == 2 else 1), dev, "mats")
+    with torch.cuda.device(dev):
+        rc = _lib.load().pwc_cv_warp_perspective_u8(frames_u8.data_ptr(), out.data_ptr(), n, H, W, h, w, mp, 9 if mats.dim() == 2 else 0,
+                                                    sbs, dbs, _stream(frames_u8))
+    check(rc, "pwc_cv_warp_perspective_u8")
     return out
 
 
