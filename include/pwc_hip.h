@@ -577,6 +577,23 @@ int pwc_cv_resize_flow_f32(const void *src, void *dst, int n, int in_h, int in_w
 int pwc_cv_warp_perspective_u8(const void *src_u8, void *dst_u8, int n, int H, int W, int h, int w, const double *mat9, int mat_stride,
                                int64_t src_bstride, int64_t dst_bstride, void *stream);
 
+/* Raw video frames -> network input (ABI v13 addition, csrc/pwc_video.hip): frame_to_tensor + pad_to_multiple_of_64 of
+ * pwc_extract_flow_video.py:27-42 as one kernel (host mirror: opticalflow_amd/video.py frame_to_tensor + kitti.pad_to_64; as NumPy in
+ * tests/video_ingest_oracle.py).
+ * frames_u8 uint8 [n][H][W][3] (interleaved, dense frames) with a free batch stride in BYTES: a frame may be one slot of a larger
+ * buffer, and since rows are 3 * W bytes NO alignment of the source is assumed.  x float [n][3][Hp][Wp] planes, Hp / Wp = H / W rounded
+ * up to multiples of 64, batch stride in ELEMENTS.
+ *   x[f][c][y][x'] = (float)S[f][min(y, H - 1)][min(x', W - 1)][bgr ? 2 - c : c] / 255.0f
+ * as an IEEE float32 division, correctly rounded (a multiplication by 1 / 255 differs for 126 of the 256 byte values); the clamped
+ * source coordinate is the replicate padding at the bottom and right.
+ * One launch for the n frames: a thread owns four consecutive output columns of one row in the three planes and stores 16 bytes per
+ * plane; its twelve source bytes are read as three dwords when they start on a dword boundary inside the row, as bytes otherwise.
+ * 64-bit indexing throughout.  Neither allocates nor synchronises; can be captured in a graph.
+ * PWC_EINVAL, nothing launched: a null pointer, n < 1, H or W outside 1..2^20, src_bstride < 3*H*W, x_bstride < 3*Hp*Wp.
+ * PWC_EALIGN, nothing launched: x not 16-byte aligned or x_bstride not a multiple of 4. */
+int pwc_video_ingest_u8(const void *frames_u8, void *x, int n, int H, int W, int bgr, int64_t src_bstride, int64_t x_bstride,
+                        void *stream);
+
 /* KITTI scoring on the device (ABI v13 additions, csrc/pwc_kitti_score.hip): EPE and Fl-all of inference_kitti.py:94-128
  * (epe_metric / fl_all_metric) straight from the network's quarter-resolution flow, nothing image-sized written unless asked for.
  * flow_q [n][2][Hq][Wq] f32 (dense planes, batch stride in elements).  Per pixel (b, y, x) of the out_h x out_w grid, in fp32 with

@@ -54,6 +54,23 @@ def _frames_dense(t: torch.Tensor, name: str) -> int:
     return sb if n > 1 else 3 * H * W
 
 
+def _raw_frames_shape(t, name: str) -> Tuple[int, int, int]:
+    """(n, H, W) of raw frames: a uint8 tensor [n,H,W,3] with positive sizes, wherever it lives.  Says which property fails (TypeError
+    for the dtype); _frames_dense then checks placement and strides."""
+    if not torch.is_tensor(t):
+        raise TypeError("%s must be a torch tensor, got %s" % (name, type(t).__name__))
+    if t.dtype != torch.uint8:
+        raise TypeError("%s must be uint8 (raw frames), got %s" % (name, t.dtype))
+    if t.dim() != 4:
+        raise ValueError("%s must be 4-D [n,H,W,3], got %s" % (name, tuple(t.shape)))
+    if t.shape[3] != 3:
+        raise ValueError("%s must have 3 interleaved channels last [n,H,W,3], got %s" % (name, tuple(t.shape)))
+    n, H, W, _ = t.shape
+    if min(n, H, W) <= 0:
+        raise ValueError("%s: every size must be positive, got %s" % (name, tuple(t.shape)))
+    return n, H, W
+
+
 def densify(t: torch.Tensor) -> torch.Tensor:
     """Return t if its C,H,W planes are dense (batch stride free), else a contiguous copy."""
     if t.dim() == 4:

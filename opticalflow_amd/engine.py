@@ -593,13 +593,17 @@ class VideoDriver:
         self._carry()
         self.primed = True
 
-    def push(self, frames: torch.Tensor) -> torch.Tensor:
-        """B new frames [B,3,H,W] -> flows of the pairs (previous, frames[0]), (frames[0], frames[1]), ..."""
+    def push(self, frames: torch.Tensor, tail=None) -> torch.Tensor:
+        """B new frames [B,3,H,W] -> flows of the pairs (previous, frames[0]), (frames[0], frames[1]), ...
+        tail: a callable that finishes the decoder and returns the flow (engine_strict.PwcVideoPlanStrict: the half-precision level 2 of
+        a trunk2=False plan).  It runs BEFORE the carry, which with c1_in_arena (batch 1) overwrites the c1 channels of the arenas."""
         if not self.primed:
             raise RuntimeError("%s.push before prime(first_frame)" % type(self).__name__)
         f = self._check(frames, self.B)
         self._pyramid([(f, 1, self.B + 1)], 1, self.B + 1)
         out = self._decode()
+        if tail is not None:
+            out = tail()
         self._carry()
         return out
 

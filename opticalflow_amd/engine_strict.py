@@ -27,6 +27,9 @@ on the GPU 0.33 / 0.57 / 0.83e-3 -- and 1.03e-3 on the smooth KITTI-like pair of
 base channels (``whatif``: 0.85 -> 0.65e-3 at 448x1024; the rest is conv2_* 0.52, dc_conv* 0.39, adding in quadrature).
 
 No autograd; ``flows()`` gives the training-mode 5-tuple (flow3..flow6 straight from the fp32 plan).
+
+``PwcVideoPlanStrict`` is the same mode for video.FlowStream: the fp32 part is engine.PwcVideoPlan (one pyramid pass per frame), the
+half-precision level 2 is this plan's ``_level2``.
 """
 from __future__ import annotations
 
@@ -37,7 +40,7 @@ import torch
 
 from . import ops
 from . import ops_f16 as F16
-from .engine import CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PwcPlan
+from .engine import CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PwcPlan, PwcVideoPlan
 from .engine_f16 import BASE_G, CORR_G, DENSE_G, _groups, context_filters, level_filters, prepare_params
 
 
@@ -75,12 +78,14 @@ PLAIN_FILTERS = parse_plain_filters(os.environ.get("PWC_STRICT_PLAIN", ""))
 
 
 class PwcPlanStrict:
+    UPPER = PwcPlan                                                 # the fp32 upper part's plan class (PwcVideoPlanStrict: the stream's)
+
     def __init__(self, params: Dict[str, torch.Tensor], B: int, H: int, W: int, device: torch.device, md: int = 4,
                  normalize_corr: bool = False, align_corners: bool = False, variant: str = "dc"):
         if md != 4:
             raise NotImplementedError("the half-precision arena is laid out for md=4 (81 cost-volume channels)")
         # fp32 part: pyramid, levels 6..3, level-2 entry
-        self.upper = PwcPlan(params, B, H, W, device, torch.float32, md, normalize_corr, align_corners, "hip", variant, trunk2=False)
+        self.upper = self.UPPER(params, B, H, W, device, torch.float32, md, normalize_corr, align_corners, "hip", variant, trunk2=False)
         self.B, self.H, self.W, self.device = B, H, W, device
         self.nd = 81
         h2, w2 = H >> 2, W >> 2
@@ -139,6 +144,11 @@ class PwcPlanStrict:
         # levels 6..3 (level 3's heads write up_flow / up_feat into the fp32 level-2 base channels) and the level-2 entry:
         # c1 | fused warp + correlation + LeakyReLU, all fp32
         up._decode()
+        return self._level2()
+
+    def _level2(self) -> torch.Tensor:
+        """The half-precision part, from the upper plan's level-2 base channels to flow2 (PwcVideoPlanStrict.push ends with it too)."""
+        up = self.upper
         # hand-over: fp32 NCHW [corr 81 | c1 32 | up_flow 2 | up_feat 2] -> the c8 half arena's corr / c1 / flow groups + residuals
         base = up.arena[2]
         c = PYRAMID_CH[2]
@@ -165,3 +175,30 @@ class PwcPlanStrict:
         """(flow2, flow3, flow4, flow5, flow6) of the last run -- the training-mode return (PWCNet.py:270-271)."""
         f = self.upper.flow
         return (self.flow_out, f[3], f[4], f[5], f[6])
+
+
+class PwcVideoPlanStrict(PwcPlanStrict):
+    """The strict mode for consecutive frames (video.FlowStream with precision="fp16-strict"): the fp32 upper part is
+    engine.PwcVideoPlan(trunk2=False) -- B + 1 pyramid slots, slot 0 carrying the previous push's last frame, one pyramid pass per frame,
+    stopping after the level-2 entry -- and the half-precision level 2 is PwcPlanStrict's, the same statement.  Against the pairwise
+    strict forward only the pyramid's batch size differs (B instead of 2B images), as between PwcVideoPlan and PwcPlan."""
+    UPPER = PwcVideoPlan
+
+    @property
+    def primed(self) -> bool:
+        return self.upper.primed
+
+    @property
+    def pyr_a(self):
+        """the upper plan's pyramid buffers: pyr_a[l][0] is the carry slot a graph capture saves and restores"""
+        return self.upper.pyr_a
+
+    def prime(self, frame: torch.Tensor) -> None:
+        self.upper.prime(frame)
+
+    def push(self, frames: torch.Tensor) -> torch.Tensor:
+        # pyramid of the B new frames, levels 6..3, level-2 entry; then the half part, and only then the carry
+        return self.upper.push(frames, tail=self._level2)
+
+    def run(self, x):
+        raise RuntimeError("PwcVideoPlanStrict is driven by prime()/push(), not run()")

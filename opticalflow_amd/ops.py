@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from ._args import (_bias_arg, _dtype_code, _f32_dense, _frames_dense, _kitti_gt_arg, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr,
-                    _query_bytes, _require_device, _scalar_arg, _scratch, _stream, _table_arg, _workspace_args, densify)
+                    _query_bytes, _raw_frames_shape, _require_device, _scalar_arg, _scratch, _stream, _table_arg, _workspace_args, densify)
 from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F32, PwcHipError, check)
 
 def corr_output_shape(C: int, H: int, W: int, pad_size: int, kernel_size: int, max_displacement: int,
@@ -644,6 +644,29 @@ def cv_warp_perspective(frames_u8: torch.Tensor, mats: torch.Tensor, out: torch.
         rc = _lib.load().pwc_cv_warp_perspective_u8(frames_u8.data_ptr(), out.data_ptr(), n, H, W, h, w, mp, 9 if mats.dim() == 2 else 0,
                                                     sbs, dbs, _stream(frames_u8))
     check(rc, "pwc_cv_warp_perspective_u8")
+    return out
+
+
+def video_ingest(frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None, bgr: bool = True) -> torch.Tensor:
+    """Raw frames uint8 [n,H,W,3] on the device (dense frames, free batch stride: e.g. one slot of a larger buffer) -> float32
+    [n,3,Hp,Wp] (Hp, Wp = H, W rounded up to multiples of 64): channel flip when `bgr`, byte / 255 as an IEEE division, HWC -> CHW and
+    replicate padding at the bottom / right -- frame_to_tensor + pad_to_multiple_of_64 of pwc_extract_flow_video.py:27-42 as one kernel
+    (C-ABI pwc_video_ingest_u8).  out: dense planes with a free batch stride.  Every argument is checked before the library loads."""
+    n, H, W = _raw_frames_shape(frames_u8, "frames_u8")
+    Hp, Wp = (H + 63) // 64 * 64, (W + 63) // 64 * 64
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, 3, Hp, Wp):
+            raise ValueError("out must be float32 %s, got %s %s" % ((n, 3, Hp, Wp), getattr(out, "dtype", type(out).__name__),
+                                                                   tuple(getattr(out, "shape", ()))))
+        if out.device != frames_u8.device:
+            raise ValueError("out is on %s, frames_u8 on %s" % (out.device, frames_u8.device))
+    _require_device(frames_u8, "frames_u8")
+    sbs = _frames_dense(frames_u8, "frames_u8")
+    out = _out_arg(out, (n, 3, Hp, Wp), torch.float32, frames_u8.device)
+    bso = _plane_dense(out, "out")
+    with torch.cuda.device(frames_u8.device):
+        rc = _lib.load().pwc_video_ingest_u8(frames_u8.data_ptr(), out.data_ptr(), n, H, W, 1 if bgr else 0, sbs, bso, _stream(frames_u8))
+    check(rc, "pwc_video_ingest_u8")
     return out
 
 

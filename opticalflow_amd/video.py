@@ -10,19 +10,27 @@ Pre/post-processing helpers follow the reference script:
   * ``pad_to_multiple_of_64`` replicate-pad bottom/right                 (:36-42, same as kitti.pad_to_64)
   * ``unpad``             the reference crops the QUARTER-resolution flow by the FULL-resolution pad
                           (:44-47, :213) -- reproduced as is (kitti.model_infer documents the same quirk)
+
+The first two run on the host and upload float32, four times the bytes of the frame.  ``ingest_frames`` is the same arithmetic as one
+HIP kernel on raw uint8 frames (csrc/pwc_video.hip, bit for bit the host helpers' result), and ``RawFlowStream`` is a FlowStream whose
+push starts from raw frames: upload of the bytes, ingest, network, pictures and vanishing point as one graph replay.
+``flow_video(..., ingest="hip")`` and ``flow_video_rendered(..., ingest="hip")`` select it; ``flow_video_vanishing`` is the per-frame
+loop of pwc_extract_flow_video_vanishpoint.py up to the drawing.
 """
 from __future__ import annotations
 
-from typing import Iterable, Iterator, Optional, Tuple
+from typing import Iterable, Iterator, NamedTuple, Optional, Tuple
 
 import numpy as np
 import torch
 
+from . import ops
 from .engine import PwcVideoPlan
 from .flowviz import Renderer, RenderSpec
 from .kitti import pad_to_64, unpad as _unpad
 
-__all__ = ["FlowStream", "RenderSpec", "frame_to_tensor", "flow_video", "flow_video_rendered"]
+__all__ = ["FlowStream", "RawFlowStream", "RawGeometry", "RenderSpec", "frame_to_tensor", "flow_video", "flow_video_rendered",
+           "flow_video_vanishing", "ingest_frames", "raw_geometry"]
 
 
 def frame_to_tensor(frame: np.ndarray) -> torch.Tensor:
@@ -31,6 +39,36 @@ def frame_to_tensor(frame: np.ndarray) -> torch.Tensor:
         raise ValueError("expected an (H,W,3) BGR frame, got %s" % (frame.shape,))
     rgb = frame[:, :, ::-1].astype(np.float32) / 255.0
     return torch.from_numpy(np.ascontiguousarray(np.transpose(rgb, (2, 0, 1))))
+
+
+def ingest_frames(frames_u8: torch.Tensor, bgr: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Raw frames uint8 [n,H,W,3] (or one [H,W,3]) on the device -> float32 [n,3,Hp,Wp]: ``frame_to_tensor`` (with bgr; bgr=False keeps
+    the channel order) + ``pad_to_64`` as one HIP kernel, the same bits.  frames_u8 may be a view with a batch stride, out likewise."""
+    if torch.is_tensor(frames_u8) and frames_u8.dim() == 3:
+        frames_u8 = frames_u8.unsqueeze(0)
+    return ops.video_ingest(frames_u8, out=out, bgr=bgr)
+
+
+class RawGeometry(NamedTuple):
+    height: int                 # Hp: the frame's height rounded up to a multiple of 64 (what the network sees)
+    width: int                  # Wp
+    pads: Tuple[int, int]       # (pad_h, pad_w) of pad_to_multiple_of_64
+    crop: Tuple[int, int]       # (Hp/4 - pad_h, Wp/4 - pad_w): the part of the quarter-resolution flow the reference keeps
+
+
+def raw_geometry(frame_h: int, frame_w: int) -> RawGeometry:
+    """Padded size, pads and the reference's crop for frames of this size (pwc_extract_flow_video.py:36-47, 213: the FULL-resolution
+    pad comes off the QUARTER-resolution flow).  A frame so small against its pad that nothing would be left is refused."""
+    H, W = int(frame_h), int(frame_w)
+    if H < 1 or W < 1:
+        raise ValueError("frame size must be positive, got %dx%d" % (H, W))
+    pad_h, pad_w = (64 - H % 64) % 64, (64 - W % 64) % 64
+    Hp, Wp = H + pad_h, W + pad_w
+    crop = (Hp // 4 - pad_h, Wp // 4 - pad_w)
+    if crop[0] < 1 or crop[1] < 1:
+        raise ValueError("a %dx%d frame pads by (%d, %d) to %dx%d: cropping the quarter-resolution flow by the full-resolution pad, as "
+                         "the reference does, leaves nothing" % (H, W, pad_h, pad_w, Hp, Wp))
+    return RawGeometry(Hp, Wp, (pad_h, pad_w), crop)
 
 
 class FlowStream:
@@ -53,9 +91,10 @@ class FlowStream:
         self.device = p0.device
         self.batch, self.height, self.width = batch, height, width
         if getattr(net, "precision", "fp32") == "fp16-strict":
-            raise NotImplementedError("FlowStream has plans for precision 'fp32' and 'fp16'; the strict half-precision mode is built "
-                                      "for PWCDCNet.forward (pairs / KITTI stream)")
-        if getattr(net, "precision", "fp32") == "fp16":
+            from .engine_strict import PwcVideoPlanStrict
+            self.plan = PwcVideoPlanStrict(params, batch, height, width, self.device, net.md, net.normalize_corr,
+                                           net.align_corners, getattr(net, "variant", "dc"))
+        elif getattr(net, "precision", "fp32") == "fp16":
             from .engine_f16 import PwcVideoPlanF16
             self.plan = PwcVideoPlanF16(params, batch, height, width, self.device, net.md, net.normalize_corr,
                                         net.align_corners, getattr(net, "variant", "dc"))
@@ -95,29 +134,150 @@ class FlowStream:
             if tuple(frames.shape) != tuple(self._static.shape):
                 raise ValueError("expected frames %s, got %s" % (tuple(self._static.shape), tuple(frames.shape)))
             self._static.copy_(frames)
-            if self._graph is None:
-                # warm-up outside capture would advance the carry slot: save and restore it around the capture
-                keep = {l: self.plan.pyr_a[l][0].clone() for l in range(2, 7)}
-                side = torch.cuda.Stream(device=self.device)
-                side.wait_stream(torch.cuda.current_stream(self.device))
-                with torch.cuda.stream(side):
-                    self._push(self._static)
-                torch.cuda.current_stream(self.device).wait_stream(side)
-                for l, t in keep.items():
-                    self.plan.pyr_a[l][0].copy_(t)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    self._push(self._static)
-                for l, t in keep.items():
-                    self.plan.pyr_a[l][0].copy_(t)
-                self._graph = graph
-            self._graph.replay()
-            return self.plan.flow_out
+            return self._replay(self._static)
+
+    def _replay(self, src: torch.Tensor) -> torch.Tensor:
+        """One push from the static input buffer `src` as a graph replay (captured on the first call)."""
+        if self._graph is None:
+            # warm-up outside capture would advance the carry slot: save and restore it around the capture (the strict plan's pyr_a
+            # is its fp32 upper plan's)
+            keep = {l: self.plan.pyr_a[l][0].clone() for l in range(2, 7)}
+            side = torch.cuda.Stream(device=self.device)
+            side.wait_stream(torch.cuda.current_stream(self.device))
+            with torch.cuda.stream(side):
+                self._push(src)
+            torch.cuda.current_stream(self.device).wait_stream(side)
+            for l, t in keep.items():
+                self.plan.pyr_a[l][0].copy_(t)
+            graph = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(graph):
+                self._push(src)
+            for l, t in keep.items():
+                self.plan.pyr_a[l][0].copy_(t)
+            self._graph = graph
+        self._graph.replay()
+        return self.plan.flow_out
 
 
-def flow_video(net, frames: Iterable[np.ndarray], use_graph: bool = True) -> Iterator[np.ndarray]:
+class RawFlowStream(FlowStream):
+    """A FlowStream whose push starts from raw frames: uint8 [batch,frame_h,frame_w,3] as cv2 decodes them (bgr=True; False for RGB).
+
+    The stream owns a static uint8 device buffer for the frames and two pinned host staging slots; each slot's reuse is guarded by an
+    event, so a push waits for the upload two pushes back at the most, never for the previous replay's.  It pads to multiples of 64
+    itself (`height`, `width`, `pads`) and knows the reference's crop (`crop`, see raw_geometry).  One push is one replay: ingest kernel
+    -> pyramid and decoder -> renderer (`render`, a RenderSpec whose crop is filled in here and whose quiver's frame_hw defaults to the
+    frame) -> VanishingEstimator.run on the arrows' vec when `vanishing` is given: a dict of the estimator's keyword arguments
+    (min_mag, max_points, grid_size, min_pairs, seed; step, if given, must be the quiver's), which needs a quiver in `render`.
+    Results are static buffers reused by every push: the returned flow (uncropped, [batch,2,Hp/4,Wp/4]), `rendered`, `points`.
+    Nothing inside the replay allocates or synchronises.
+    """
+
+    def __init__(self, net, batch: int, frame_h: int, frame_w: int, bgr: bool = True, render: Optional[RenderSpec] = None,
+                 vanishing: Optional[dict] = None, use_graph: bool = True):
+        geo = raw_geometry(frame_h, frame_w)
+        self.frame_h, self.frame_w, self.bgr = int(frame_h), int(frame_w), bool(bgr)
+        self.pads, self.crop = geo.pads, geo.crop
+        if render is not None:
+            qkw = None
+            if render.quiver is not None:
+                qkw = dict(render.quiver)
+                qkw.setdefault("frame_hw", (self.frame_h, self.frame_w))
+            render = render._replace(crop=geo.crop, quiver=qkw)
+        if vanishing is not None and (render is None or render.quiver is None):
+            raise ValueError("vanishing needs the arrow grid: give a RenderSpec with a quiver")
+        super().__init__(net, batch, geo.height, geo.width, use_graph=use_graph, render=render)
+        self._raw = torch.empty((batch, self.frame_h, self.frame_w, 3), dtype=torch.uint8, device=self.device)
+        self._stage = [torch.empty((batch, self.frame_h, self.frame_w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self._stage_done = [None, None]         # per slot: the event recorded behind the upload that last read it
+        self._slot = 0
+        self.estimator = None
+        self.points = None
+        if vanishing is not None:
+            from .vanishing import VanishingEstimator
+            kw, q = dict(vanishing), render.quiver
+            if int(kw.setdefault("step", q.get("step", 16))) != int(q.get("step", 16)):
+                raise ValueError("vanishing step %s differs from the quiver's %s" % (kw["step"], q.get("step", 16)))
+            if "frame_hw" in kw or "device" in kw or "batch" in kw:
+                raise ValueError("vanishing takes step, min_mag, max_points, grid_size, min_pairs, seed; the rest is the stream's")
+            self.estimator = VanishingEstimator(batch, tuple(q["frame_hw"]), device=self.device, **kw)
+
+    def _push(self, raw: torch.Tensor) -> torch.Tensor:
+        ops.video_ingest(raw, out=self._static, bgr=self.bgr)
+        flow = super()._push(self._static)
+        if self.estimator is not None:
+            self.points = self.estimator.run(self.rendered.arrows.vec)
+        return flow
+
+    def _as_frames(self, frames, n: int) -> torch.Tensor:
+        t = torch.from_numpy(np.ascontiguousarray(frames)) if isinstance(frames, np.ndarray) else frames
+        if not torch.is_tensor(t):
+            raise TypeError("frames must be a NumPy array or a tensor, got %s" % type(frames).__name__)
+        if t.dim() == 3:
+            t = t.unsqueeze(0)
+        if t.dtype != torch.uint8 or tuple(t.shape) != (n, self.frame_h, self.frame_w, 3):
+            raise ValueError("expected uint8 frames %s, got %s %s" % ((n, self.frame_h, self.frame_w, 3), t.dtype, tuple(t.shape)))
+        return t
+
+    def _upload(self, t: torch.Tensor) -> None:
+        """frames -> the static device buffer, on the current stream (so behind the previous replay, which reads that buffer)"""
+        if t.is_cuda:
+            self._raw.copy_(t)
+            return
+        k, self._slot = self._slot, self._slot ^ 1
+        if self._stage_done[k] is None:
+            self._stage_done[k] = torch.cuda.Event()
+        else:
+            self._stage_done[k].synchronize()       # the upload two pushes back has read this slot
+        self._stage[k].copy_(t)
+        self._raw.copy_(self._stage[k], non_blocking=True)
+        self._stage_done[k].record(torch.cuda.current_stream(self.device))
+
+    def prime(self, frame) -> None:
+        """First frame of the sequence: uint8 [frame_h,frame_w,3] or [1,frame_h,frame_w,3], NumPy, CPU tensor or device tensor."""
+        t = self._as_frames(frame, 1).to(self.device)
+        with torch.no_grad():
+            self.plan.prime(ops.video_ingest(t, bgr=self.bgr))
+
+    def push(self, frames) -> torch.Tensor:
+        """``batch`` further raw frames; returns [batch,2,Hp/4,Wp/4] like FlowStream.push (a view of the plan's output buffer; the
+        reference's result is its top-left `crop`)."""
+        t = self._as_frames(frames, self.batch)
+        if not self.plan.primed:
+            raise RuntimeError("RawFlowStream.push before prime(first_frame)")
+        with torch.no_grad(), torch.cuda.device(self.device):
+            self._upload(t)
+            return self._replay(self._raw) if self.use_graph else self._push(self._raw)
+
+
+def _check_ingest(ingest: str) -> bool:
+    if ingest not in ("host", "hip"):
+        raise ValueError("ingest must be 'host' or 'hip', got %r" % (ingest,))
+    return ingest == "hip"
+
+
+def _raw_frame(frame: np.ndarray, stream: Optional["RawFlowStream"]) -> np.ndarray:
+    if frame.ndim != 3 or frame.shape[2] != 3:
+        raise ValueError("expected an (H,W,3) BGR frame, got %s" % (frame.shape,))
+    if stream is not None and tuple(frame.shape[:2]) != (stream.frame_h, stream.frame_w):
+        raise ValueError("frame size changed mid-stream")
+    return frame
+
+
+def flow_video(net, frames: Iterable[np.ndarray], use_graph: bool = True, ingest: str = "host") -> Iterator[np.ndarray]:
     """Generator over BGR uint8 frames yielding one (h,w,2) float32 flow per consecutive pair, exactly
-    what ``process_frame_pair`` returns for (frame_t, frame_t+1) (pwc_extract_flow_video.py:192-216)."""
+    what ``process_frame_pair`` returns for (frame_t, frame_t+1) (pwc_extract_flow_video.py:192-216).
+    ingest="hip": the raw frame is uploaded and prepared on the device (RawFlowStream); the same numbers."""
+    if _check_ingest(ingest):
+        raw: Optional[RawFlowStream] = None
+        for frame in frames:
+            _raw_frame(frame, raw)
+            if raw is None:
+                raw = RawFlowStream(net, 1, frame.shape[0], frame.shape[1], bgr=True, use_graph=use_graph)
+                raw.prime(frame)
+                continue
+            flow = _unpad(raw.push(frame), raw.pads[0], raw.pads[1])
+            yield flow.squeeze(0).permute(1, 2, 0).contiguous().cpu().numpy()
+        return
     stream: Optional[FlowStream] = None
     pads: Tuple[int, int] = (0, 0)
     for frame in frames:
@@ -136,13 +296,38 @@ def flow_video(net, frames: Iterable[np.ndarray], use_graph: bool = True) -> Ite
         yield flow.squeeze(0).permute(1, 2, 0).contiguous().cpu().numpy()
 
 
+def _rendered_dict(stream: FlowStream, flow: torch.Tensor, with_flow: bool) -> dict:
+    r, out = stream.rendered, {}
+    if r.color is not None:
+        out["color"] = r.color[0].cpu().numpy()
+    if r.arrows is not None:
+        out["vec"], out["tip"], out["flags"] = (a[0].cpu().numpy() for a in r.arrows)
+    if with_flow:
+        ch, cw = stream.renderer.crop
+        out["flow"] = flow[0, :, :ch, :cw].permute(1, 2, 0).contiguous().cpu().numpy()
+    return out
+
+
 def flow_video_rendered(net, frames: Iterable[np.ndarray], color: bool = True, quiver: Optional[dict] = None, use_graph: bool = True,
-                        clip_flow: Optional[float] = None, dominant: bool = False, with_flow: bool = False) -> Iterator[dict]:
+                        clip_flow: Optional[float] = None, dominant: bool = False, with_flow: bool = False,
+                        ingest: str = "host") -> Iterator[dict]:
     """flow_video that hands back pictures instead of the float flow: per consecutive pair a dict with "color" (h,w,3) uint8 RGB (the
     colour wheel of pwc_extract_flow.py's flow_to_color) when `color`, and "vec" (Gy,Gx,2) float32, "tip" (Gy,Gx,2) int32, "flags"
     (Gy,Gx) uint8 when `quiver` is given: the keyword arguments of flowviz.quiver_arrows (step, scale, min_mag, style, ...;
     frame_hw defaults to the frame's size).  Both are made on the device from the same cropped quarter-resolution flow flow_video
-    yields, and only they are downloaded; with_flow=True adds "flow", exactly flow_video's array."""
+    yields, and only they are downloaded; with_flow=True adds "flow", exactly flow_video's array.  ingest="hip": raw frames are
+    uploaded and prepared on the device (RawFlowStream); the same results."""
+    if _check_ingest(ingest):
+        raw: Optional[RawFlowStream] = None
+        for frame in frames:
+            _raw_frame(frame, raw)
+            if raw is None:
+                spec = RenderSpec(color=color, clip_flow=clip_flow, quiver=quiver, dominant=dominant)
+                raw = RawFlowStream(net, 1, frame.shape[0], frame.shape[1], bgr=True, render=spec, use_graph=use_graph)
+                raw.prime(frame)
+                continue
+            yield _rendered_dict(raw, raw.push(frame), with_flow)
+        return
     stream: Optional[FlowStream] = None
     for frame in frames:
         t = frame_to_tensor(frame).unsqueeze(0)
@@ -161,13 +346,28 @@ def flow_video_rendered(net, frames: Iterable[np.ndarray], color: bool = True, q
             continue
         if tuple(tp.shape[2:]) != (stream.height, stream.width):
             raise ValueError("frame size changed mid-stream")
-        flow = stream.push(tp.to(stream.device))
-        r, out = stream.rendered, {}
-        if r.color is not None:
-            out["color"] = r.color[0].cpu().numpy()
-        if r.arrows is not None:
-            out["vec"], out["tip"], out["flags"] = (a[0].cpu().numpy() for a in r.arrows)
-        if with_flow:
-            ch, cw = stream.renderer.crop
-            out["flow"] = flow[0, :, :ch, :cw].permute(1, 2, 0).contiguous().cpu().numpy()
+        yield _rendered_dict(stream, stream.push(tp.to(stream.device)), with_flow)
+
+
+def flow_video_vanishing(net, frames: Iterable[np.ndarray], step: int = 16, scale: float = 1, min_mag: float = 1, use_graph: bool = True,
+                         with_flow: bool = False, **vanishing) -> Iterator[dict]:
+    """The per-frame loop of pwc_extract_flow_video_vanishpoint.py (process_video -> create_quiver_frame(..., draw_vanishing_point=True),
+    :258-367, :502-530) up to the drawing: per consecutive pair of BGR uint8 frames a dict with the arrow grid "vec" (Gy,Gx,2) float32,
+    "tip" (Gy,Gx,2) int32, "flags" (Gy,Gx) uint8 and "vanishing": (vx, vy, prob) as the reference's
+    estimate_vanishing_point_from_flow(flow, step, min_mag) returns them, or None where it returns None.  Raw frames go up, the ingest,
+    the network, the arrows and the estimate are one replay (RawFlowStream); **vanishing are VanishingEstimator's remaining arguments
+    (max_points, grid_size, min_pairs, seed; vanishing.py says how its subsampling differs from np.random.choice).  with_flow=True adds
+    "flow", flow_video's array.  The shrink canvas and the drawing are the caller's."""
+    from .vanishing import to_host
+    raw: Optional[RawFlowStream] = None
+    for frame in frames:
+        _raw_frame(frame, raw)
+        if raw is None:
+            spec = RenderSpec(color=False, quiver=dict(step=step, scale=scale, min_mag=min_mag, style="video"))
+            raw = RawFlowStream(net, 1, frame.shape[0], frame.shape[1], bgr=True, render=spec,
+                                vanishing=dict(vanishing, min_mag=min_mag), use_graph=use_graph)
+            raw.prime(frame)
+            continue
+        out = _rendered_dict(raw, raw.push(frame), with_flow)
+        out["vanishing"] = to_host(raw.points)[0]
         yield out
