@@ -17,6 +17,7 @@ import torch
 
 from . import ops
 from ._args import _require_device
+from ._pipeline import PinnedRing
 
 # pwc_augment_params: the inverted matrix (fp64), the forward linear part (fp32), crop origin, the sample's size, flags
 PARAMS_DTYPE = np.dtype([("m", "<f8", (6,)), ("a", "<f4", (4,)), ("y0", "<i4"), ("x0", "<i4"), ("h", "<i4"), ("w", "<i4"),
@@ -218,15 +219,15 @@ class StagedAugmenter:
         shapes = [((batch, 2, Hs, Ws, 3), torch.uint8),
                   ((batch, Hs, Ws, 3), torch.uint16) if gt_kind == 1 else ((batch, 2, Hs, Ws), torch.float32),
                   ((batch, Hs, Ws), torch.uint8), ((batch, self.dtype.itemsize), torch.uint8)]
-        self._host = [torch.zeros(s, dtype=d).pin_memory() for s, d in shapes]
-        self._views = [t.numpy() for t in self._host]
+        self._ring, self._specs = PinnedRing(1), shapes                # one staging slot of four tensors, zeroed once
+        self._host = self._ring.acquire(*shapes)
+        self._views = [t.zero_().numpy() for t in self._host]
         self._dev = [torch.zeros(s, dtype=d, device=self.device) for s, d in shapes]
         self.x = torch.empty((batch, 6, ch, cw), dtype=torch.float32, device=self.device)
         self.flow = torch.empty((batch, 2, ch, cw), dtype=torch.float32, device=self.device)
         self._third = torch.empty((batch, 1, ch, cw), dtype=torch.float32, device=self.device)
         setattr(self, self.third, self._third)
         self.status = torch.zeros(batch, dtype=torch.int32, device=self.device)
-        self._uploaded = None
         self._n, self._with_valid = 0, False
 
     def stage(self, samples, params: Optional[np.ndarray] = None) -> np.ndarray:
@@ -234,9 +235,7 @@ class StagedAugmenter:
         n = len(samples)
         if not 1 <= n <= self.batch:
             raise ValueError("expected 1..%d samples, got %d" % (self.batch, n))
-        if self._uploaded is not None:
-            self._uploaded.synchronize()           # the copy that last read the staging memory must be done before it is rewritten
-            self._uploaded = None
+        self._ring.acquire(*self._specs)                   # the copy that last read the staging memory is done before it is rewritten
         fr, gt, va, _ = self._views
         _, _, v, sizes = pack_slots(samples, self.slot_hw, self.gt_kind, frames=fr[:n], gt=gt[:n], valid=va[:n])
         if params is None:
@@ -258,8 +257,7 @@ class StagedAugmenter:
         with torch.cuda.device(self.device):
             for i in use:
                 self._dev[i][:n].copy_(self._host[i][:n], non_blocking=True)
-            self._uploaded = torch.cuda.Event()
-            self._uploaded.record()
+            self._ring.mark()
 
     def run(self):
         """The kernel alone, on the device slots as they are, on the current stream -> views of the n staged samples in (x, flow, third

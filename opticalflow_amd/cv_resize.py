@@ -177,10 +177,12 @@ class CvGraphedInfer(GraphedInfer):
         prepare((height, width), (h_, w_), device)                              # resident before the capture
         prepare((h_ // 4, w_ // 4), (height, width), device)
 
+    def _pairs(self) -> torch.Tensor:
+        """The uint8 pairs [batch,2,H,W,3] the ingest reads (a subclass prepares them first)."""
+        return self.static_u8
+
     def _body(self) -> torch.Tensor:
         h, w = self.static_u8.shape[2:4]
-        x = ingest_pairs(self.static_u8, True, out=self.x_in)
-        out = self.model(x)
-        self.flow_quarter = out[0] if isinstance(out, (tuple, list)) else out
+        flow = self._forward(ingest_pairs(self._pairs(), True, out=self.x_in))
         m = MODES[self.mode]
-        return resize_flow(self.flow_quarter, (h, w), m["gain"], True, m["layout"], out=self.flow_full)
+        return resize_flow(flow, (h, w), m["gain"], True, m["layout"], out=self.flow_full)

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import ops
-from .cv_resize import MODES, CvGraphedInfer, _check_frames, ingest_pairs, resize_flow
+from .cv_resize import CvGraphedInfer, _check_frames
 
 
 # ------------------------------------------------------------------ host helpers (no GPU, no torch needed)
@@ -148,14 +148,9 @@ class TopviewInfer(CvGraphedInfer):
         h, w = self.static_u8.shape[2:4]
         ops.cv_warp_perspective(self.static_u8.view(2 * self.batch, h, w, 3), self.mats, self.warped.view(2 * self.batch, h, w, 3))
 
-    def _body(self) -> torch.Tensor:
-        h, w = self.static_u8.shape[2:4]
-        self._warp()
-        x = ingest_pairs(self.warped, True, out=self.x_in)                      # from here on CvGraphedInfer's body, fed the warped pairs
-        out = self.model(x)
-        self.flow_quarter = out[0] if isinstance(out, (tuple, list)) else out
-        m = MODES[self.mode]
-        return resize_flow(self.flow_quarter, (h, w), m["gain"], True, m["layout"], out=self.flow_full)
+    def _pairs(self) -> torch.Tensor:
+        self._warp()                                                            # CvGraphedInfer's body, fed the warped pairs
+        return self.warped
 
 
 class _StreamInfer(TopviewInfer):

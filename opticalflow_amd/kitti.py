@@ -20,6 +20,7 @@ raw totals is downloaded at the end.  `evaluate_pairs` is the reference's host l
 """
 from __future__ import annotations
 
+import functools
 import os
 import struct
 import zlib
@@ -30,6 +31,7 @@ import torch
 import torch.nn.functional as F
 
 from . import ops
+from ._pipeline import PinnedRing, capture_graph, pad64
 
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -37,8 +39,7 @@ IMAGENET_STD = (0.229, 0.224, 0.225)
 
 # ------------------------------------------------------------------ geometry
 def pad_to_64(x: torch.Tensor) -> Tuple[torch.Tensor, int, int]:
-    h, w = x.shape[-2:]
-    ph, pw = (64 - h % 64) % 64, (64 - w % 64) % 64
+    ph, pw = pad64(*x.shape[-2:])[2:]
     if ph == 0 and pw == 0:
         return x, 0, 0
     return F.pad(x, (0, pw, 0, ph), mode="replicate"), ph, pw
@@ -88,13 +89,18 @@ def normalize_pair(img1_u8: torch.Tensor, img2_u8: torch.Tensor) -> Tuple[torch.
     return outs[0], outs[1]
 
 
+def _flow_of(model, x: torch.Tensor) -> torch.Tensor:
+    """The model's flow for x: the finest level, which comes first in the training tuple."""
+    out = model(x)
+    return out[0] if isinstance(out, (tuple, list)) else out
+
+
 @torch.no_grad()
 def model_infer(model, img1: torch.Tensor, img2: torch.Tensor, reference_unpad: bool = True) -> torch.Tensor:
     """img1, img2: [1,3,H,W] normalised images on the model's device -> flow [1,2,H,W] (network units, no x20)."""
     h, w = img1.shape[-2:]
     x, ph, pw = pad_to_64(torch.cat([img1, img2], dim=1))
-    out = model(x)
-    flow = out[0] if isinstance(out, (tuple, list)) else out          # finest level first in the training tuple
+    flow = _flow_of(model, x)
     if flow.is_cuda and flow.dtype == torch.float32:
         # unpad + bilinear resize + rescale as one kernel (the same one the captured pipeline uses; tests hold it to flow_resize)
         hq, wq = flow.shape[-2:]
@@ -228,6 +234,11 @@ def _host_u8(img) -> torch.Tensor:
     return t
 
 
+@functools.lru_cache(maxsize=None)
+def _torch_dtype(np_dtype) -> torch.dtype:
+    return torch.from_numpy(np.empty(0, np_dtype)).dtype
+
+
 class _Ingest:
     """Host uint8 pairs -> device batches [n,2,H,W,3], one batch ahead of the consumer.
 
@@ -244,15 +255,11 @@ class _Ingest:
     def __init__(self, pairs, device: torch.device, batch: int, n_extra: int = 0):
         self.pairs, self.device, self.batch, self.n_extra = iter(pairs), device, batch, n_extra
         self.copy_stream = torch.cuda.Stream(device=device)
-        self.slots = [None, None]          # pinned host staging, allocated on first use per shape
-        self.views = [None, None]          # the same memory as numpy arrays [2*batch, H, W, 3]
-        self.uploaded = [None, None]       # event of the last upload that read each staging buffer
-        # n_extra > 0: every item is (img1, img2, e_0 .. e_{n_extra-1}), the e_k numpy arrays of one shape and dtype per k (the
-        # ground truth of evaluate_stream); they are staged and uploaded with the images and handed out by batches_with_extra()
-        self.xslots = [None, None]         # per staging buffer: pinned tensors [batch, *e_k.shape]
-        self.xviews = [None, None]
+        # two pinned staging slots, allocated on first use per shape: the images [batch,2,H,W,3] and, with n_extra > 0 (every item is (img1,
+        # img2, e_0 .. e_{n_extra-1}), numpy arrays of one shape and dtype per k: evaluate_stream's ground truth), tensors [batch, *e_k.shape]
+        self.ring, self._views = PinnedRing(2), {}
 
-    def _fill(self, slot: int):
+    def _fill(self):
         imgs, extras = [], []
         for item in self.pairs:
             a, b = _host_u8(item[0]), _host_u8(item[1])
@@ -267,36 +274,30 @@ class _Ingest:
         if not imgs:
             return None
         n, (h, w) = len(imgs) // 2, imgs[0].shape[:2]
-        shape = (self.batch, 2, h, w, 3)
-        if self.slots[slot] is None or tuple(self.slots[slot].shape) != shape:
-            self.slots[slot] = torch.empty(shape, dtype=torch.uint8).pin_memory()
-            self.views[slot] = self.slots[slot].view(2 * self.batch, h, w, 3).numpy()
-        elif self.uploaded[slot] is not None:
-            self.uploaded[slot].synchronize()      # the DMA that last read this buffer must be done before it is rewritten
+        specs = [((self.batch, 2, h, w, 3), torch.uint8)]
+        specs += [((self.batch,) + e.shape, _torch_dtype(e.dtype)) for e in map(np.asarray, extras[0])]
+        slot, *xslots = self.ring.acquire(*specs)  # waits until the DMA that last read this slot is done, before it is rewritten
+        if slot not in self._views:                # the same memory as numpy arrays, made once per allocation (tensors hash by identity)
+            if len(self._views) == 2:              # a new shape: the views of the allocations it replaces go
+                self._views.clear()
+            self._views[slot] = [slot.view(2 * self.batch, h, w, 3).numpy()] + [t.numpy() for t in xslots]
+        views = self._views[slot]
         for i, img in enumerate(imgs):             # straight into pinned memory (an intermediate torch.stack cost 5 ms/pair)
-            np.copyto(self.views[slot][i], img.numpy()[..., :3])
-        if self.n_extra:
-            first = [np.asarray(e) for e in extras[0]]
-            if self.xslots[slot] is None or any(tuple(t.shape[1:]) != e.shape for t, e in zip(self.xslots[slot], first)):
-                self.xslots[slot] = [torch.from_numpy(np.empty((self.batch,) + e.shape, e.dtype)).pin_memory() for e in first]
-                self.xviews[slot] = [t.numpy() for t in self.xslots[slot]]
-            for i, ex in enumerate(extras):
-                for view, e in zip(self.xviews[slot], ex):
-                    np.copyto(view[i], e, casting="no")
+            np.copyto(views[0][i], img.numpy()[..., :3])
+        for i, ex in enumerate(extras):
+            for xview, e in zip(views[1:], ex):
+                np.copyto(xview[i], e, casting="no")
         with torch.cuda.stream(self.copy_stream):
-            dev = self.slots[slot][:n].to(self.device, non_blocking=True)
-            xdev = tuple(t[:n].to(self.device, non_blocking=True) for t in self.xslots[slot]) if self.n_extra else ()
-            ev = torch.cuda.Event()
-            ev.record(self.copy_stream)
-        self.uploaded[slot] = ev
-        return dev, ev, xdev
+            dev = slot[:n].to(self.device, non_blocking=True)
+            xdev = tuple(t[:n].to(self.device, non_blocking=True) for t in xslots)
+        # the slot's event: the consumer waits on it before the slot comes round again and the event is recorded anew
+        return dev, self.ring.mark(self.copy_stream), xdev
 
     def batches_with_extra(self) -> Iterator[Tuple[torch.Tensor, Tuple[torch.Tensor, ...]]]:
-        pending, slot = self._fill(0), 1
+        pending = self._fill()
         while pending is not None:
             dev, ev, xdev = pending
-            pending = self._fill(slot)             # batch k+1 is staged and its upload started before batch k is consumed
-            slot ^= 1
+            pending = self._fill()                 # batch k+1 is staged and its upload started before batch k is consumed
             cur = torch.cuda.current_stream(self.device)
             cur.wait_event(ev)
             dev.record_stream(cur)
@@ -305,8 +306,7 @@ class _Ingest:
             yield dev, xdev
 
     def batches(self) -> Iterator[torch.Tensor]:
-        for dev, _ in self.batches_with_extra():
-            yield dev
+        return (dev for dev, _ in self.batches_with_extra())
 
 
 class PairStream(_Ingest):
@@ -334,18 +334,11 @@ class GraphedInfer:
     def __init__(self, model, height: int, width: int, device: torch.device, reference_unpad: bool = True, batch: int = 1):
         self.model, self.reference_unpad, self.batch = model, reference_unpad, batch
         self.static_u8 = torch.zeros((batch, 2, height, width, 3), dtype=torch.uint8, device=device)
-        self.x_in = torch.empty((batch, 6, (height + 63) // 64 * 64, (width + 63) // 64 * 64), dtype=torch.float32, device=device)
+        self.x_in = torch.empty((batch, 6) + pad64(height, width)[:2], dtype=torch.float32, device=device)
         self._alloc_outputs(height, width, device)
         keep, model.use_graph = getattr(model, "use_graph", False), False      # no nested capture
         try:
-            side = torch.cuda.Stream(device=device)
-            side.wait_stream(torch.cuda.current_stream(device))
-            with torch.cuda.stream(side):
-                self._body()                                                  # builds the plan, first-launch attributes
-            torch.cuda.current_stream(device).wait_stream(side)
-            self.graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self.graph):
-                self.out = self._body()
+            self.graph, self.out = capture_graph(self._body, device)           # the warm-up run builds the plan
         finally:
             model.use_graph = keep
 
@@ -356,36 +349,43 @@ class GraphedInfer:
         """Last kernel of the captured pipeline: quarter-resolution flow -> what the graph hands out (ScoredInfer scores here instead)."""
         return ops.flow_upsample(self.flow_quarter, ch, cw, h, w, out=self.flow_full)
 
+    def _forward(self, x: torch.Tensor) -> torch.Tensor:
+        """The model on x; its output [batch,2,H_/4,W_/4] (a static buffer like `out`) stays in ``flow_quarter`` (a sharded stream gathers it)."""
+        self.flow_quarter = _flow_of(self.model, x)
+        return self.flow_quarter
+
     def _body(self) -> torch.Tensor:
         h, w = self.static_u8.shape[2:4]
-        ph, pw = (64 - h % 64) % 64, (64 - w % 64) % 64
+        ph, pw = pad64(h, w)[2:]
         if os.environ.get("PWC_KITTI_TORCH_PREPOST") == "1":
             # the same steps as ~30 PyTorch launches (what round 2 captured; kept for A/B runs and as the statement the kernels are tested against)
             i1, i2 = normalize_pair(self.static_u8[:, 0], self.static_u8[:, 1])
             x, ph, pw = pad_to_64(torch.cat([i1, i2], dim=1))
-            out = self.model(x)
-            self.flow_quarter = out[0] if isinstance(out, (tuple, list)) else out
+            self._forward(x)
             flow = unpad(self.flow_quarter, ph, pw) if self.reference_unpad else unpad(self.flow_quarter, ph // 4, pw // 4)
             return flow_resize(flow, h, w)
         # ToTensor + normalisation + cat + replicate pad as ONE kernel, unpad + bilinear resize + rescale as another (csrc/pwc_kitti.hip):
         # as PyTorch launches they were 14.6 % of the fp16 stream's GPU time
-        x = ops.kitti_ingest(self.static_u8, IMAGENET_MEAN, IMAGENET_STD, out=self.x_in)
-        out = self.model(x)
-        # the network's own output [batch,2,H_/4,W_/4] (a static buffer like `out`): what a sharded stream gathers
-        self.flow_quarter = out[0] if isinstance(out, (tuple, list)) else out
+        self._forward(ops.kitti_ingest(self.static_u8, IMAGENET_MEAN, IMAGENET_STD, out=self.x_in))
         hq, wq = self.flow_quarter.shape[-2:]
         ch, cw = (hq - ph, wq - pw) if self.reference_unpad else (hq - ph // 4, wq - pw // 4)
         self.crop = (ch, cw)                       # the top-left part of flow_quarter that is stretched to (h, w)
         return self._tail(ch, cw, h, w)
 
+    def _check_pairs(self, pairs_u8: torch.Tensor) -> int:
+        """n of uint8 pairs [n<=batch,2,H,W,3] of this pipeline's size; anything else is refused."""
+        n = pairs_u8.shape[0]
+        if pairs_u8.dim() != 5 or tuple(pairs_u8.shape[1:]) != tuple(self.static_u8.shape[1:]) or pairs_u8.dtype != torch.uint8 \
+                or not 1 <= n <= self.batch:
+            raise ValueError("expected uint8 [n<=%d,%s], got %s %s" % (self.batch, ",".join(map(str, self.static_u8.shape[1:])),
+                                                                      pairs_u8.dtype, tuple(pairs_u8.shape)))
+        return n
+
     def __call__(self, pair_u8: torch.Tensor) -> torch.Tensor:
         """pair_u8: [2,H,W,3] (one pair) or [n,2,H,W,3] with n <= batch; returns the first n flows [n,2,H,W]."""
         if pair_u8.dim() == 4:
             pair_u8 = pair_u8.unsqueeze(0)
-        n = pair_u8.shape[0]
-        if tuple(pair_u8.shape[1:]) != tuple(self.static_u8.shape[1:]) or pair_u8.dtype != torch.uint8 or not 1 <= n <= self.batch:
-            raise ValueError("expected uint8 [n<=%d,%s], got %s %s" % (self.batch, ",".join(map(str, self.static_u8.shape[1:])),
-                                                                      pair_u8.dtype, tuple(pair_u8.shape)))
+        n = self._check_pairs(pair_u8)
         self.static_u8[:n].copy_(pair_u8, non_blocking=True)
         self.graph.replay()
         return self.out[:n]
@@ -457,11 +457,7 @@ class ScoredInfer(GraphedInfer):
         """pairs_u8 [n<=batch,2,H,W,3] uint8 and the ground truth of those n pairs on the device (a uint16 tensor, or (flow planes,
         validity)); fills table[row0:row0+n] and returns the float32 scores [n,2] = (EPE, Fl-all) (a static buffer)."""
         gt = tuple(gt) if isinstance(gt, (tuple, list)) else (gt,)
-        n = pairs_u8.shape[0]
-        if pairs_u8.dim() != 5 or tuple(pairs_u8.shape[1:]) != tuple(self.static_u8.shape[1:]) or pairs_u8.dtype != torch.uint8 \
-                or not 1 <= n <= self.batch:
-            raise ValueError("expected uint8 [n<=%d,%s], got %s %s" % (self.batch, ",".join(map(str, self.static_u8.shape[1:])),
-                                                                      pairs_u8.dtype, tuple(pairs_u8.shape)))
+        n = self._check_pairs(pairs_u8)
         if len(gt) != len(self.static_gt) or any(tuple(g.shape) != (n,) + tuple(st.shape[1:]) for g, st in zip(gt, self.static_gt)):
             raise ValueError("ground truth does not match the %r form %s of this pipeline" % (self.gt_form, [tuple(st.shape[1:]) for st in self.static_gt]))
         if not 0 <= row0 <= self.table.shape[0] - n:

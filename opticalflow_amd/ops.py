@@ -19,6 +19,7 @@ from . import _lib
 from ._args import (_bias_arg, _dtype_code, _f32_dense, _frames_dense, _kitti_gt_arg, _mask_arg, _out_arg, _packed_arg, _plane_dense, _ptr,
                     _query_bytes, _raw_frames_shape, _require_device, _scalar_arg, _scratch, _stream, _table_arg, _workspace_args, densify)
 from ._lib import (FLAG_ACT_LEAKY, FLAG_CONV_RESIDUAL, FLAG_CORR_NORMALIZE, PWC_F32, PwcHipError, check)
+from ._pipeline import pad64
 
 def corr_output_shape(C: int, H: int, W: int, pad_size: int, kernel_size: int, max_displacement: int,
                       stride1: int, stride2: int) -> Tuple[int, int, int]:
@@ -470,7 +471,7 @@ def kitti_ingest(pairs_u8: torch.Tensor, mean, std, out: Optional[torch.Tensor] 
             or not pairs_u8.is_contiguous():
         raise ValueError("pairs_u8 must be a contiguous uint8 device tensor [n,2,H,W,3]")
     n, _, H, W, _ = pairs_u8.shape
-    Hp, Wp = (H + 63) // 64 * 64, (W + 63) // 64 * 64
+    Hp, Wp = pad64(H, W)[:2]
     out = _out_arg(out, (n, 6, Hp, Wp), torch.float32, pairs_u8.device)
     bso = _plane_dense(out, "out")
     m3 = (ctypes.c_float * 3)(*[float(v) for v in mean])
@@ -653,7 +654,7 @@ def video_ingest(frames_u8: torch.Tensor, out: Optional[torch.Tensor] = None, bg
     replicate padding at the bottom / right -- frame_to_tensor + pad_to_multiple_of_64 of pwc_extract_flow_video.py:27-42 as one kernel
     (C-ABI pwc_video_ingest_u8).  out: dense planes with a free batch stride.  Every argument is checked before the library loads."""
     n, H, W = _raw_frames_shape(frames_u8, "frames_u8")
-    Hp, Wp = (H + 63) // 64 * 64, (W + 63) // 64 * 64
+    Hp, Wp = pad64(H, W)[:2]
     if out is not None:
         if not torch.is_tensor(out) or out.dtype != torch.float32 or tuple(out.shape) != (n, 3, Hp, Wp):
             raise ValueError("out must be float32 %s, got %s %s" % ((n, 3, Hp, Wp), getattr(out, "dtype", type(out).__name__),

@@ -19,6 +19,8 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
+from ._pipeline import PinnedRing
+
 PRECISION_BITS = 22          # 32 - 8 - 2: Pillow's fixed point for 8-bit images
 IMAGENET_MEAN = (0.485, 0.456, 0.406)
 IMAGENET_STD = (0.229, 0.224, 0.225)
@@ -222,20 +224,8 @@ class FrameIngest:
         self.batch = int(batch)
         if self.batch <= 0:
             raise ValueError("batch must be positive")
-        self._slots = [None, None]
-        self._events = [None, None]
-        self._turn = 0
+        self._ring = PinnedRing(2)
         self._dev = None
-
-    def _slot(self, H: int, W: int) -> Tuple[torch.Tensor, int]:
-        i = self._turn
-        self._turn ^= 1
-        shape = (2 * self.batch, H, W, 3)
-        if self._slots[i] is None or tuple(self._slots[i].shape) != shape:
-            self._slots[i] = torch.empty(shape, dtype=torch.uint8, pin_memory=True)
-        elif self._events[i] is not None:
-            self._events[i].synchronize()          # the upload that last read this slot has finished
-        return self._slots[i], i
 
     def pairs(self, frames1, frames2, out: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """frames1 / frames2: B host frames each ([B,H,W,3] uint8 tensor / array, or a sequence of [H,W,3]), all of one size ->
@@ -249,16 +239,14 @@ class FrameIngest:
             if f.dtype != torch.uint8 or tuple(f.shape) != (H, W, 3):
                 raise ValueError("all frames of one call must be uint8 [%d,%d,3]; got %s %s" % (H, W, f.dtype, tuple(f.shape)))
         _check_supported((H, W), self.size)
-        slot, i = self._slot(H, W)
+        slot, = self._ring.acquire(((2 * self.batch, H, W, 3), torch.uint8))     # waits until the upload that last read it is done
         for j, f in enumerate(fr):
             slot[j].copy_(f)
         if self._dev is None or tuple(self._dev.shape) != tuple(slot.shape):
             self._dev = torch.empty(slot.shape, dtype=torch.uint8, device=self.device)
         dev = self._dev[:2 * B]
         dev.copy_(slot[:2 * B], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record(torch.cuda.current_stream(self.device))
-        self._events[i] = ev
+        self._ring.mark(torch.cuda.current_stream(self.device))
         h, w = self.size
         if out is None:
             out = torch.empty((B, 6, h, w), dtype=torch.float32, device=self.device)
@@ -277,7 +265,5 @@ def infer_resized(model, frames1_u8: torch.Tensor, frames2_u8: torch.Tensor, ima
     x = torch.empty((B, 6, h, w), dtype=torch.float32, device=frames1_u8.device)
     resize_frames(frames1_u8, (h, w), mean, std, out=x[:, :3])
     resize_frames(frames2_u8, (h, w), mean, std, out=x[:, 3:])
-    flow = model(x)
-    if isinstance(flow, (list, tuple)):
-        flow = flow[0]
-    return resize_flow(flow, (H, W))
+    from .kitti import _flow_of
+    return resize_flow(_flow_of(model, x), (H, W))

@@ -40,6 +40,7 @@ import torch.nn as nn
 
 from . import ops
 from ._lib import PwcHipError
+from ._pipeline import capture_graph
 from .correlation import Correlation, onnx_correlation_enabled
 from .engine import (CONTEXT, DENSE_OUT, LEAKY, PYRAMID_CH, PYRAMID_NAMES, PYRAMID_NAMES_OLD, WARP_SCALE, PwcBidirPlan, PwcPlan,
                      level_in_channels)
@@ -320,16 +321,8 @@ class PWCDCNet(nn.Module):
         if entry is None:
             static_in = torch.empty_like(x, memory_format=torch.contiguous_format)
             static_in.copy_(x)
-            side = torch.cuda.Stream(device=x.device)
-            side.wait_stream(torch.cuda.current_stream(x.device))
-            with torch.cuda.stream(side):           # warm-up outside capture (first-launch attributes)
-                plan.run(static_in)
-            torch.cuda.current_stream(x.device).wait_stream(side)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                plan.run(static_in)
-            entry = (graph, static_in)
-            self._graphs[key] = entry
+            graph, _ = capture_graph(lambda: plan.run(static_in), x.device)     # one warm-up run (first-launch attributes), then the capture
+            entry = self._graphs[key] = (graph, static_in)
         graph, static_in = entry
         if x.data_ptr() != static_in.data_ptr():        # a caller that fills graph_input() in place skips this copy
             static_in.copy_(x)

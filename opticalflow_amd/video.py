@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import ops
+from ._pipeline import PinnedRing, capture_graph, pad64
 from .engine import PwcVideoPlan
 from .flowviz import Renderer, RenderSpec
 from .kitti import pad_to_64, unpad as _unpad
@@ -60,10 +61,7 @@ def raw_geometry(frame_h: int, frame_w: int) -> RawGeometry:
     """Padded size, pads and the reference's crop for frames of this size (pwc_extract_flow_video.py:36-47, 213: the FULL-resolution
     pad comes off the QUARTER-resolution flow).  A frame so small against its pad that nothing would be left is refused."""
     H, W = int(frame_h), int(frame_w)
-    if H < 1 or W < 1:
-        raise ValueError("frame size must be positive, got %dx%d" % (H, W))
-    pad_h, pad_w = (64 - H % 64) % 64, (64 - W % 64) % 64
-    Hp, Wp = H + pad_h, W + pad_w
+    Hp, Wp, pad_h, pad_w = pad64(H, W)
     crop = (Hp // 4 - pad_h, Wp // 4 - pad_w)
     if crop[0] < 1 or crop[1] < 1:
         raise ValueError("a %dx%d frame pads by (%d, %d) to %dx%d: cropping the quarter-resolution flow by the full-resolution pad, as "
@@ -142,21 +140,19 @@ class FlowStream:
             # warm-up outside capture would advance the carry slot: save and restore it around the capture (the strict plan's pyr_a
             # is its fp32 upper plan's)
             keep = {l: self.plan.pyr_a[l][0].clone() for l in range(2, 7)}
-            side = torch.cuda.Stream(device=self.device)
-            side.wait_stream(torch.cuda.current_stream(self.device))
-            with torch.cuda.stream(side):
-                self._push(src)
-            torch.cuda.current_stream(self.device).wait_stream(side)
-            for l, t in keep.items():
-                self.plan.pyr_a[l][0].copy_(t)
-            graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
-                self._push(src)
-            for l, t in keep.items():
-                self.plan.pyr_a[l][0].copy_(t)
-            self._graph = graph
+
+            def restore():
+                for l, t in keep.items():
+                    self.plan.pyr_a[l][0].copy_(t)
+            self._graph, _ = capture_graph(lambda: self._push(src), self.device, between=restore)
         self._graph.replay()
         return self.plan.flow_out
+
+
+def _frame_render(render: Optional[RenderSpec], crop: Tuple[int, int], frame_hw: Tuple[int, int]) -> Optional[RenderSpec]:
+    """`render` for frames of one size: the crop filled in, the quiver's frame_hw defaulting to the frame."""
+    q = None if render is None or render.quiver is None else dict({"frame_hw": frame_hw}, **render.quiver)
+    return None if render is None else render._replace(crop=crop, quiver=q)
 
 
 class RawFlowStream(FlowStream):
@@ -177,19 +173,14 @@ class RawFlowStream(FlowStream):
         geo = raw_geometry(frame_h, frame_w)
         self.frame_h, self.frame_w, self.bgr = int(frame_h), int(frame_w), bool(bgr)
         self.pads, self.crop = geo.pads, geo.crop
-        if render is not None:
-            qkw = None
-            if render.quiver is not None:
-                qkw = dict(render.quiver)
-                qkw.setdefault("frame_hw", (self.frame_h, self.frame_w))
-            render = render._replace(crop=geo.crop, quiver=qkw)
+        render = _frame_render(render, geo.crop, (self.frame_h, self.frame_w))
         if vanishing is not None and (render is None or render.quiver is None):
             raise ValueError("vanishing needs the arrow grid: give a RenderSpec with a quiver")
         super().__init__(net, batch, geo.height, geo.width, use_graph=use_graph, render=render)
         self._raw = torch.empty((batch, self.frame_h, self.frame_w, 3), dtype=torch.uint8, device=self.device)
-        self._stage = [torch.empty((batch, self.frame_h, self.frame_w, 3), dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self._stage_done = [None, None]         # per slot: the event recorded behind the upload that last read it
-        self._slot = 0
+        self._ring = PinnedRing(2)
+        for _ in range(2):                      # both staging slots are pinned here, not in the first two pushes
+            self._ring.acquire((self._raw.shape, torch.uint8))
         self.estimator = None
         self.points = None
         if vanishing is not None:
@@ -223,14 +214,10 @@ class RawFlowStream(FlowStream):
         if t.is_cuda:
             self._raw.copy_(t)
             return
-        k, self._slot = self._slot, self._slot ^ 1
-        if self._stage_done[k] is None:
-            self._stage_done[k] = torch.cuda.Event()
-        else:
-            self._stage_done[k].synchronize()       # the upload two pushes back has read this slot
-        self._stage[k].copy_(t)
-        self._raw.copy_(self._stage[k], non_blocking=True)
-        self._stage_done[k].record(torch.cuda.current_stream(self.device))
+        stage, = self._ring.acquire((self._raw.shape, torch.uint8))     # waits until the upload two pushes back has read this slot
+        stage.copy_(t)
+        self._raw.copy_(stage, non_blocking=True)
+        self._ring.mark(torch.cuda.current_stream(self.device))
 
     def prime(self, frame) -> None:
         """First frame of the sequence: uint8 [frame_h,frame_w,3] or [1,frame_h,frame_w,3], NumPy, CPU tensor or device tensor."""
@@ -249,50 +236,53 @@ class RawFlowStream(FlowStream):
             return self._replay(self._raw) if self.use_graph else self._push(self._raw)
 
 
-def _check_ingest(ingest: str) -> bool:
+class _HostStream:
+    """ingest="host" behind the part of RawFlowStream the frame loops use (batch 1): ``frame_to_tensor`` + ``pad_to_64`` on the host, the
+    float32 frame uploaded, a plain FlowStream.  What this path costs is the baseline tools/bench_video_ingest.py reports against."""
+
+    def __init__(self, net, batch: int, frame_h: int, frame_w: int, render: Optional[RenderSpec] = None, use_graph: bool = True):
+        Hp, Wp, pad_h, pad_w = pad64(frame_h, frame_w)
+        self.frame_h, self.frame_w, self.pads = frame_h, frame_w, (pad_h, pad_w)
+        self.crop = (Hp // 4 - pad_h, Wp // 4 - pad_w)     # the reference's unpad: the full-resolution pad off the quarter-resolution map
+        self._stream = FlowStream(net, batch, Hp, Wp, use_graph=use_graph, render=_frame_render(render, self.crop, (frame_h, frame_w)))
+        self.renderer = self._stream.renderer
+
+    rendered = property(lambda self: self._stream.rendered)
+
+    def _upload(self, frame: np.ndarray) -> torch.Tensor:
+        return pad_to_64(frame_to_tensor(frame).unsqueeze(0))[0].to(self._stream.device)
+
+    def prime(self, frame: np.ndarray) -> None:
+        self._stream.prime(self._upload(frame))
+
+    def push(self, frame: np.ndarray) -> torch.Tensor:
+        return self._stream.push(self._upload(frame))
+
+
+def _pushes(frames: Iterable[np.ndarray], ingest: str, net, **kw):
+    """The per-frame loop of the flow_video family: the stream (RawFlowStream for ingest="hip", _HostStream for "host", batch 1, **kw)
+    is built for the first frame's size and primed with it; every further frame is pushed, yielding (stream, flow)."""
     if ingest not in ("host", "hip"):
         raise ValueError("ingest must be 'host' or 'hip', got %r" % (ingest,))
-    return ingest == "hip"
-
-
-def _raw_frame(frame: np.ndarray, stream: Optional["RawFlowStream"]) -> np.ndarray:
-    if frame.ndim != 3 or frame.shape[2] != 3:
-        raise ValueError("expected an (H,W,3) BGR frame, got %s" % (frame.shape,))
-    if stream is not None and tuple(frame.shape[:2]) != (stream.frame_h, stream.frame_w):
-        raise ValueError("frame size changed mid-stream")
-    return frame
+    stream = None
+    for frame in frames:
+        if frame.ndim != 3 or frame.shape[2] != 3:
+            raise ValueError("expected an (H,W,3) BGR frame, got %s" % (frame.shape,))
+        if stream is None:
+            stream = (RawFlowStream if ingest == "hip" else _HostStream)(net, 1, frame.shape[0], frame.shape[1], **kw)
+            stream.prime(frame)
+        elif tuple(frame.shape[:2]) != (stream.frame_h, stream.frame_w):
+            raise ValueError("frame size changed mid-stream")
+        else:
+            yield stream, stream.push(frame)
 
 
 def flow_video(net, frames: Iterable[np.ndarray], use_graph: bool = True, ingest: str = "host") -> Iterator[np.ndarray]:
     """Generator over BGR uint8 frames yielding one (h,w,2) float32 flow per consecutive pair, exactly
     what ``process_frame_pair`` returns for (frame_t, frame_t+1) (pwc_extract_flow_video.py:192-216).
     ingest="hip": the raw frame is uploaded and prepared on the device (RawFlowStream); the same numbers."""
-    if _check_ingest(ingest):
-        raw: Optional[RawFlowStream] = None
-        for frame in frames:
-            _raw_frame(frame, raw)
-            if raw is None:
-                raw = RawFlowStream(net, 1, frame.shape[0], frame.shape[1], bgr=True, use_graph=use_graph)
-                raw.prime(frame)
-                continue
-            flow = _unpad(raw.push(frame), raw.pads[0], raw.pads[1])
-            yield flow.squeeze(0).permute(1, 2, 0).contiguous().cpu().numpy()
-        return
-    stream: Optional[FlowStream] = None
-    pads: Tuple[int, int] = (0, 0)
-    for frame in frames:
-        t = frame_to_tensor(frame).unsqueeze(0)
-        tp, pad_h, pad_w = pad_to_64(t)
-        if stream is None:
-            dev = next(net.parameters()).device
-            stream = FlowStream(net, 1, tp.shape[2], tp.shape[3], use_graph=use_graph)
-            pads = (pad_h, pad_w)
-            stream.prime(tp.to(dev))
-            continue
-        if tuple(tp.shape[2:]) != (stream.height, stream.width):
-            raise ValueError("frame size changed mid-stream")
-        flow = stream.push(tp.to(stream.device))
-        flow = _unpad(flow, pads[0], pads[1])     # full-resolution pad, like the reference
+    for stream, flow in _pushes(frames, ingest, net, use_graph=use_graph):
+        flow = _unpad(flow, stream.pads[0], stream.pads[1])     # full-resolution pad, like the reference
         yield flow.squeeze(0).permute(1, 2, 0).contiguous().cpu().numpy()
 
 
@@ -317,36 +307,9 @@ def flow_video_rendered(net, frames: Iterable[np.ndarray], color: bool = True, q
     frame_hw defaults to the frame's size).  Both are made on the device from the same cropped quarter-resolution flow flow_video
     yields, and only they are downloaded; with_flow=True adds "flow", exactly flow_video's array.  ingest="hip": raw frames are
     uploaded and prepared on the device (RawFlowStream); the same results."""
-    if _check_ingest(ingest):
-        raw: Optional[RawFlowStream] = None
-        for frame in frames:
-            _raw_frame(frame, raw)
-            if raw is None:
-                spec = RenderSpec(color=color, clip_flow=clip_flow, quiver=quiver, dominant=dominant)
-                raw = RawFlowStream(net, 1, frame.shape[0], frame.shape[1], bgr=True, render=spec, use_graph=use_graph)
-                raw.prime(frame)
-                continue
-            yield _rendered_dict(raw, raw.push(frame), with_flow)
-        return
-    stream: Optional[FlowStream] = None
-    for frame in frames:
-        t = frame_to_tensor(frame).unsqueeze(0)
-        tp, pad_h, pad_w = pad_to_64(t)
-        if stream is None:
-            dev = next(net.parameters()).device
-            hq, wq = tp.shape[2] // 4, tp.shape[3] // 4
-            crop = (hq - pad_h, wq - pad_w)           # the reference's unpad: the full-resolution pad off the quarter-resolution map
-            qkw = None
-            if quiver is not None:
-                qkw = dict(quiver)
-                qkw.setdefault("frame_hw", tuple(frame.shape[:2]))
-            spec = RenderSpec(color=color, clip_flow=clip_flow, quiver=qkw, dominant=dominant, crop=crop)
-            stream = FlowStream(net, 1, tp.shape[2], tp.shape[3], use_graph=use_graph, render=spec)
-            stream.prime(tp.to(dev))
-            continue
-        if tuple(tp.shape[2:]) != (stream.height, stream.width):
-            raise ValueError("frame size changed mid-stream")
-        yield _rendered_dict(stream, stream.push(tp.to(stream.device)), with_flow)
+    spec = RenderSpec(color=color, clip_flow=clip_flow, quiver=quiver, dominant=dominant)
+    for stream, flow in _pushes(frames, ingest, net, render=spec, use_graph=use_graph):
+        yield _rendered_dict(stream, flow, with_flow)
 
 
 def flow_video_vanishing(net, frames: Iterable[np.ndarray], step: int = 16, scale: float = 1, min_mag: float = 1, use_graph: bool = True,
@@ -359,15 +322,8 @@ def flow_video_vanishing(net, frames: Iterable[np.ndarray], step: int = 16, scal
     (max_points, grid_size, min_pairs, seed; vanishing.py says how its subsampling differs from np.random.choice).  with_flow=True adds
     "flow", flow_video's array.  The shrink canvas and the drawing are the caller's."""
     from .vanishing import to_host
-    raw: Optional[RawFlowStream] = None
-    for frame in frames:
-        _raw_frame(frame, raw)
-        if raw is None:
-            spec = RenderSpec(color=False, quiver=dict(step=step, scale=scale, min_mag=min_mag, style="video"))
-            raw = RawFlowStream(net, 1, frame.shape[0], frame.shape[1], bgr=True, render=spec,
-                                vanishing=dict(vanishing, min_mag=min_mag), use_graph=use_graph)
-            raw.prime(frame)
-            continue
-        out = _rendered_dict(raw, raw.push(frame), with_flow)
+    spec = RenderSpec(color=False, quiver=dict(step=step, scale=scale, min_mag=min_mag, style="video"))
+    for raw, flow in _pushes(frames, "hip", net, render=spec, vanishing=dict(vanishing, min_mag=min_mag), use_graph=use_graph):
+        out = _rendered_dict(raw, flow, with_flow)
         out["vanishing"] = to_host(raw.points)[0]
         yield out

@@ -28,6 +28,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 from opticalflow_amd import compare  # noqa: E402
+from opticalflow_amd._pipeline import capture_graph  # noqa: E402
 import flow_compare_oracle as FO  # noqa: E402
 
 HBM_PEAK = 8.0e12
@@ -82,18 +83,6 @@ def torch_chain(a, b):
     return torch.stack(out)
 
 
-def graph_of(fn, dev):
-    side = torch.cuda.Stream(dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        fn()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        fn()
-    return graph
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -127,7 +116,7 @@ def main():
             cmp = compare.FlowComparer(n, H, W, dev, TAUS, epe_map=with_map)
             nbytes = (16 + 4 * with_map) * n * H * W
             t = windows(lambda: cmp.run(a, b), calls)
-            tg = windows(graph_of(lambda: cmp.run(a, b), dev).replay, calls)
+            tg = windows(capture_graph(lambda: cmp.run(a, b), dev)[0].replay, calls)
             per[with_map], per_eager[with_map] = statistics.median(tg), statistics.median(t)
             for kind, tt in (("eager", t), ("graph replay", tg)):
                 m = statistics.median(tt)
@@ -136,7 +125,7 @@ def main():
                        100.0 * nbytes / (m * 1e-6) / HBM_PEAK))
         tc = windows(lambda: torch_chain(a, b), max(calls // 4, 25))
         try:
-            tcg = windows(graph_of(lambda: torch_chain(a, b), dev).replay, max(calls // 4, 25))
+            tcg = windows(capture_graph(lambda: torch_chain(a, b), dev)[0].replay, max(calls // 4, 25))
             say("%-14s (b) torch chain on the device, batch row only: eager %s; graph replay %s" % (tag, spread(tc), spread(tcg)))
         except RuntimeError as e:                                  # a chain that cannot be captured is a finding, not a failure
             tcg = [float("nan")]

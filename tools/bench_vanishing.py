@@ -23,6 +23,7 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
 sys.path.insert(0, os.path.join(REPO, "tests"))
 from opticalflow_amd import vanishing  # noqa: E402
+from opticalflow_amd._pipeline import capture_graph  # noqa: E402
 import vanishing_oracle as VO  # noqa: E402
 
 STEP = 16
@@ -85,15 +86,7 @@ def main():
         say("%-14s grid %dx%d, frame 0: status %d, N %d, pairs kept %d, device == oracle: %s"
             % (tag, gy, gx, info[0, 0], info[0, 1], info[0, 2], agree))
         t = event_times(lambda: est.run(vec))
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            est.run(vec)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            est.run(vec)
-        tg = event_times(graph.replay)
+        tg = event_times(capture_graph(lambda: est.run(vec), dev)[0].replay)
         say("%-14s (a) device, 3 launches (%d + %d + %d workgroups): median %.1f us per call (min %.1f, p90 %.1f; %d calls), "
             "%.1f us per frame; graph replay median %.1f us"
             % (tag, B, 16 * B, B, statistics.median(t), t[0], t[int(0.9 * len(t))], len(t), statistics.median(t) / B, statistics.median(tg)))
