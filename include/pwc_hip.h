@@ -516,6 +516,49 @@ int pwc_pil_resize_planes_f32(const void *src, void *dst, int n, int c, int in_h
                               const int32_t *xbounds, const double *xcoef, int xksize, const int32_t *ybounds, const double *ycoef,
                               int yksize, const float *factors, int64_t src_bstride, void *stream);
 
+/* inference.py's resized flow, scored and / or encoded in the launch that resizes it (additions within ABI v13,
+ * csrc/pwc_pil_resize.hip): resize_flow (inference.py:162-190), compute_epe / compute_fl (:105-159) and the array save_flow builds
+ * (:266-282) for a batch, without a full-resolution float flow unless the caller asks for one.
+ * src float [n][2][in_h][in_w] (dense planes, free batch stride in elements); tables and factors (float [2], may be NULL) exactly as
+ * pwc_pil_resize_planes_f32 takes them with c = 2, the same supported range (pwc_pil_resize_supported), the same copy on an axis of
+ * unchanged length and the same single order, horizontal first (for Pillow's vertical-first regime the caller runs the vertical pass
+ * with pwc_pil_resize_planes_f32 and this entry point as the horizontal-only pass; opticalflow_amd/pil_resize.py eval_flow does).
+ * Per output pixel (b, y, x), fp32 with no fused multiply-add:
+ *   1. (pu, pv) = what pwc_pil_resize_planes_f32 writes there for channels 0 and 1: the two passes, then * factors[c] when factors
+ *        is not NULL (no multiply otherwise);
+ *   2. flow_out (may be NULL; float [n][2][out_h][out_w], dense): pu, pv, bit-identical to pwc_pil_resize_planes_f32;
+ *   3. enc_out (may be NULL; uint16 [n][out_h][out_w][3], dense, 2-byte aligned and no more): eu = (uint16)(int)clamp(pu * 64.0f +
+ *        32768.0f), ev alike; the cast truncates toward zero; clamp(t) = t < 0 or NaN -> 0, t > 65535 -> 65535.  The reference's
+ *        (x * 64.0 + 2**15).astype(np.uint16) is the same float32 expression and wraps modulo 2^16 out of range, where the C cast
+ *        is undefined: the clamp is a stated deviation for |flow| >= 512 px (kitti.encode_flow_rgb16 clips likewise).
+ *        enc_order 0 (save_flow's own order): the samples {1, ev, eu};  enc_order 1 (the devkit's R, G, B = u, v, valid; what
+ *        kitti.write_png16_rgb / read_png16_rgb and pwc_kitti_score use): {eu, ev, 1};
+ *   4. score, when gt is not NULL.  gt_kind 0: float planes [n][2][out_h][out_w] with valid uint8 [n][out_h][out_w] (non-zero =
+ *        valid) or NULL (all valid);  gt_kind 1: uint16 [n][out_h][out_w][3] as R, G, B = u, v, valid, decoded
+ *        ((float)s - 32768.f) / 64.f, valid = (B != 0);  gt_kind 2: the same samples in the reference's own order {valid, v, u}
+ *        (inference.py:89-102).  valid must be NULL with kinds 1 and 2.  Then as pwc_kitti_score step 3:
+ *        du = pu - gu; dv alike; epe = sqrtf(du*du + dv*dv); mag = sqrtf(gu*gu + gv*gv); OUTLIER when epe > fmaxf(3.0f, 0.05f * mag);
+ *        per sample {fp64 sum of the fp32 epe over valid pixels, int64 #valid, int64 #valid outliers}.
+ * out (device, float [n][2], needed with gt): {(float)(sum / #valid), (float)(100.0 * #outliers / #valid)}, both NaN when #valid == 0
+ * (inference.py reports 0.0 there; opticalflow_amd/inference_eval.py does that on the host from the raw counts).
+ * workspace (needed with gt): device, 8-byte aligned, pwc_pil_flow_eval_workspace_bytes(n, out_h, out_w) = 24 * n * (1 + tiles per
+ * sample) bytes (-1 for a non-positive size).  Each 16 x 64 tile leaves its three totals there, summed in a fixed tree order, and one
+ * final workgroup per sample adds that sample's tiles in order: no atomics, bit-reproducible, no host synchronisation.  After the
+ * launch its first 24 n bytes hold the raw totals, [n][3] 8-byte words: fp64 sum, int64 #valid, int64 #outliers.
+ * One workgroup resizes BOTH channels of its 16 x 64 tile: channel u is staged in LDS and finished into registers, then the same LDS
+ * stages channel v.  One launch (two with gt); neither allocates nor synchronises; can be captured in a graph.
+ * PWC_EINVAL, nothing launched: null src or table; none of gt / flow_out / enc_out; gt without workspace or out; non-positive sizes; an
+ * unsupported scale; a ksize that disagrees with the sizes; src_bstride < 2*in_h*in_w; gt_kind outside 0..2 (with gt); enc_order
+ * outside 0..1 (with enc_out); valid != NULL without gt or with gt_kind 1 / 2; n > 65535 (indexing is 64-bit throughout); a workspace that
+ * is too small.  PWC_EALIGN, nothing launched: workspace or coefficients not 8-byte, src / flow_out / out / float gt / bounds /
+ * factors not 4-byte, enc_out / uint16 gt not 2-byte aligned. */
+int64_t pwc_pil_flow_eval_workspace_bytes(int n, int out_h, int out_w);
+int pwc_pil_flow_eval(const void *src, int n, int in_h, int in_w, int out_h, int out_w, const int32_t *xbounds, const double *xcoef,
+                      int xksize, const int32_t *ybounds, const double *ycoef, int yksize, const float *factors, int64_t src_bstride,
+                      const void *gt /* may be NULL */, int gt_kind, const void *valid /* may be NULL */,
+                      void *flow_out /* may be NULL */, void *enc_out /* may be NULL */, int enc_order, void *workspace,
+                      int64_t workspace_bytes, void *out /* float [n][2] */, void *stream);
+
 /* cv2.resize-exact INTER_LINEAR resize (ABI v13 additions, csrc/pwc_cv_resize.hip): the two cv2.resize calls around the model in
  * script_pwc.py:43-83 and topview.py:79-119 (compute_flow), with what surrounds them -- channel flip, / 255, HWC -> CHW, stacking on
  * the way in; the gain (x 20 in script_pwc.py), the resize and the u / v rescale on the way out.  "Exact" means equal to this project's

@@ -14,7 +14,9 @@ from .augment import DeviceAugmenter, augment_batch  # noqa: F401
 from . import augment_full  # noqa: F401
 from .augment_full import DeviceFullAugmenter, augment_full_batch  # noqa: F401
 from . import pil_resize  # noqa: F401
-from .pil_resize import resize_flow, resize_frames  # noqa: F401
+from .pil_resize import eval_flow, resize_flow, resize_frames  # noqa: F401
+from . import inference_eval  # noqa: F401
+from .inference_eval import ResizedEval  # noqa: F401
 from . import cv_resize  # noqa: F401
 from .cv_resize import CvGraphedInfer  # noqa: F401
 from . import cv_warp  # noqa: F401

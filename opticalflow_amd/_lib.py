@@ -107,6 +107,9 @@ SIGNATURES = {
                                          c_void_p, c_int64, c_int, c_void_p]),
     "pwc_pil_resize_planes_f32": (c_int, [c_void_p] * 2 + [c_int] * 6 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int,
                                           c_void_p, c_int64, c_void_p]),
+    "pwc_pil_flow_eval_workspace_bytes": (c_int64, [c_int] * 3),
+    "pwc_pil_flow_eval": (c_int, [c_void_p] + [c_int] * 5 + [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int64,
+                                  c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int64, c_void_p, c_void_p]),
     "pwc_cv_resize_frames_u8": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 5 + [c_int, c_int64, c_int, c_void_p]),
     "pwc_cv_resize_flow_f32": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p] * 4 + [c_float] * 3 + [c_int, c_int64, c_void_p]),
     "pwc_cv_warp_perspective_u8": (c_int, [c_void_p] * 2 + [c_int] * 5 + [c_void_p, c_int, c_int64, c_int64, c_void_p]),

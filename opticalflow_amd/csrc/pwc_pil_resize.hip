@@ -23,6 +23,7 @@
 #include <stdint.h>
 #include <math.h>
 
+#include "pwc_block_reduce.h"
 #include "pwc_common.h"
 
 namespace {
@@ -167,8 +168,60 @@ pil_frames_kernel(const uint8_t *__restrict__ src, float *__restrict__ out, uint
     }
 }
 
+// The planes kernel and the flow-evaluation kernel share their three steps: the tile's slices of the tables, the horizontal stage
+// into LDS and the vertical stage of one output pixel.
 // kCopyX / kCopyY: the axis keeps its length (iw == ow / ih == oh), so Pillow takes no pass on it and the stage copies.  Compile-time,
 // so that the instantiation with both passes is the code it was before the copies existed.
+struct PlaneTables {
+    double *xk, *yk;                           // [kTW][xks], [kTH][yks]
+    int2 *xb, *yb;                             // [kTW], [kTH]
+};
+
+// the tile's table slices into LDS; ends with a barrier
+__device__ __forceinline__ void planes_load_tables(const PlaneTables &s, const int32_t *__restrict__ xb, const double *__restrict__ xk,
+                                                   int xks, const int32_t *__restrict__ yb, const double *__restrict__ yk, int yks, int iw,
+                                                   int ih, int x0, int y0, int tw, int th) {
+    const int tid = threadIdx.x;
+    if (tid < tw) s.xb[tid] = safe_bounds(xb, x0 + tid, iw, xks);
+    if (tid >= 64 && tid < 64 + th) s.yb[tid - 64] = safe_bounds(yb, y0 + tid - 64, ih, yks);
+    for (int i = tid; i < tw * xks; i += 256) s.xk[i] = xk[(int64_t)x0 * xks + i];
+    for (int i = tid; i < th * yks; i += 256) s.yk[i] = yk[(int64_t)y0 * yks + i];
+    __syncthreads();
+}
+
+// horizontal stage: source rows r0 .. r0 + rows of one plane, resampled to the tile's columns, into s_rows[rows][kTW]
+template <bool kCopyX>
+__device__ __forceinline__ void planes_stage_rows(const float *__restrict__ img, float *s_rows, const PlaneTables &s, int xks, int iw, int x0,
+                                                  int tw, int r0, int rows) {
+    for (int it = threadIdx.x; it < rows * kTW; it += 256) {
+        const int r = it >> 6, xl = it & 63;
+        float o = 0.f;
+        if (kCopyX) {                            // unchanged axis: Pillow takes no horizontal pass, the sample is copied
+            if (xl < tw) o = img[(int64_t)(r0 + r) * iw + x0 + xl];
+        } else if (xl < tw) {
+            const int2 b = s.xb[xl];
+            const float *p = img + (int64_t)(r0 + r) * iw + b.x;
+            const double *k = s.xk + xl * xks;
+            double ss = 0.0;
+            for (int t = 0; t < b.y; ++t) ss += (double)p[t] * k[t];
+            o = (float)ss;
+        }
+        s_rows[it] = o;
+    }
+}
+
+// vertical stage of output pixel (yl, xl) of the tile, from the staged rows
+template <bool kCopyY>
+__device__ __forceinline__ float planes_finish(const float *s_rows, const PlaneTables &s, int yks, int y0, int yl, int xl, int r0, int rows_cap) {
+    if (kCopyY)                                  // unchanged axis: no vertical pass, output row y is staged row y - r0
+        return s_rows[min(max(y0 + yl - r0, 0), rows_cap - 1) * kTW + xl];
+    const int2 b = s.yb[yl];
+    const double *k = s.yk + yl * yks;
+    double ss = 0.0;
+    for (int t = 0; t < b.y; ++t) ss += (double)s_rows[min(b.x - r0 + t, rows_cap - 1) * kTW + xl] * k[t];
+    return (float)ss;
+}
+
 template <bool kCopyX, bool kCopyY>
 __global__ void __launch_bounds__(256)
 pil_planes_kernel(const float *__restrict__ src, float *__restrict__ dst, int C, int ih, int iw, int oh, int ow,
@@ -177,36 +230,16 @@ pil_planes_kernel(const float *__restrict__ src, float *__restrict__ dst, int C,
     extern __shared__ __attribute__((aligned(16))) float s_rows[];          // [rows_cap][kTW]
     __shared__ double s_xk[kTW * kMaxK], s_yk[kTH * kMaxK];
     __shared__ int2 s_xb[kTW], s_yb[kTH];
+    const PlaneTables s{s_xk, s_yk, s_xb, s_yb};
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
     const int n = blockIdx.z / C, c = blockIdx.z - n * C;
     const int tw = min(kTW, ow - x0), th = min(kTH, oh - y0);
-
-    if (tid < tw) s_xb[tid] = safe_bounds(xb, x0 + tid, iw, xks);
-    if (tid >= 64 && tid < 64 + th) s_yb[tid - 64] = safe_bounds(yb, y0 + tid - 64, ih, yks);
-    for (int i = tid; i < tw * xks; i += 256) s_xk[i] = xk[(int64_t)x0 * xks + i];
-    for (int i = tid; i < th * yks; i += 256) s_yk[i] = yk[(int64_t)y0 * yks + i];
-    __syncthreads();
+    planes_load_tables(s, xb, xk, xks, yb, yk, yks, iw, ih, x0, y0, tw, th);
 
     const int r0 = s_yb[0].x;
     const int rows = min(max(s_yb[th - 1].x + s_yb[th - 1].y - r0, 0), rows_cap);
-    const float *img = src + (int64_t)n * bss + (int64_t)c * ih * iw;
-
-    for (int it = tid; it < rows * kTW; it += 256) {
-        const int r = it >> 6, xl = it & 63;
-        float o = 0.f;
-        if (kCopyX) {                            // unchanged axis: Pillow takes no horizontal pass, the sample is copied
-            if (xl < tw) o = img[(int64_t)(r0 + r) * iw + x0 + xl];
-        } else if (xl < tw) {
-            const int2 b = s_xb[xl];
-            const float *p = img + (int64_t)(r0 + r) * iw + b.x;
-            const double *k = s_xk + xl * xks;
-            double ss = 0.0;
-            for (int t = 0; t < b.y; ++t) ss += (double)p[t] * k[t];
-            o = (float)ss;
-        }
-        s_rows[it] = o;
-    }
+    planes_stage_rows<kCopyX>(src + (int64_t)n * bss + (int64_t)c * ih * iw, s_rows, s, xks, iw, x0, tw, r0, rows);
     __syncthreads();
 
     const float fac = factors ? factors[c] : 1.0f;
@@ -214,17 +247,155 @@ pil_planes_kernel(const float *__restrict__ src, float *__restrict__ dst, int C,
     for (int it = tid; it < th * kTW; it += 256) {
         const int yl = it >> 6, xl = it & 63;
         if (xl >= tw) continue;
-        float v;
-        if (kCopyY) {                            // unchanged axis: no vertical pass, output row y is staged row y - r0
-            v = s_rows[min(max(y0 + yl - r0, 0), rows_cap - 1) * kTW + xl];
-        } else {
-            const int2 b = s_yb[yl];
-            const double *k = s_yk + yl * yks;
-            double ss = 0.0;
-            for (int t = 0; t < b.y; ++t) ss += (double)s_rows[min(b.x - r0 + t, rows_cap - 1) * kTW + xl] * k[t];
-            v = (float)ss;
-        }
+        const float v = planes_finish<kCopyY>(s_rows, s, yks, y0, yl, xl, r0, rows_cap);
         o[(int64_t)yl * ow + xl] = factors ? v * fac : v;
+    }
+}
+
+// ---- inference.py's resized flow, scored and / or encoded where it is made (include/pwc_hip.h pwc_pil_flow_eval) ----
+// One workgroup makes BOTH channels of its tile: u is staged and finished into registers (lane tid owns column tid % 64 of the rows
+// tid / 64 + 4 k, the planes kernel's own mapping), then the same LDS stages v.  What follows per pixel is pwc_kitti_score's
+// arithmetic (csrc/pwc_kitti_score.hip) on a prediction that never leaves the registers.
+constexpr int kPix = kTH * kTW / 256;          // 4 pixels per lane
+using EvalRec = pwc::TilePartial<2>;           // {double sum_epe, int64 {valid, outliers}}: one per sample, then one per tile
+static_assert(sizeof(pwc::TreeLds<256, 1, 2>) <= sizeof(double) * kTW * kMaxK, "the tile reduction reuses the x coefficient slice");
+
+struct EvalOut {
+    const void *gt;
+    const uint8_t *valid;
+    float *flow;
+    uint16_t *enc;
+    EvalRec *part;
+    int enc_order;
+};
+
+// three consecutive uint16 at a 2-byte aligned address as one dword and one short, the dword wherever the address allows it
+__device__ __forceinline__ void store3_u16(uint16_t *p, uint32_t s0, uint32_t s1, uint32_t s2) {
+    if ((reinterpret_cast<uintptr_t>(p) & 2u) == 0) {
+        *reinterpret_cast<uint32_t *>(p) = s0 | (s1 << 16);
+        p[2] = (uint16_t)s2;
+    } else {
+        p[0] = (uint16_t)s0;
+        *reinterpret_cast<uint32_t *>(p + 1) = s1 | (s2 << 16);
+    }
+}
+
+// save_flow's sample: (uint16)(int)(x * 64 + 2^15) in float32, truncated toward zero; clamped to [0, 65535], NaN -> 0
+__device__ __forceinline__ uint32_t encode16(float x) {
+    const float t = x * 64.0f + 32768.0f;
+    return (uint32_t)(int)(t > 0.0f ? fminf(t, 65535.0f) : 0.0f);
+}
+
+// KIND: -1 no ground truth, 0 float planes (+ uint8 validity), 1 uint16 {u, v, valid}, 2 uint16 {valid, v, u}
+template <bool kCopyX, bool kCopyY, int KIND>
+__global__ void __launch_bounds__(256)
+pil_flow_eval_kernel(const float *__restrict__ src, int ih, int iw, int oh, int ow, const int32_t *__restrict__ xb,
+                     const double *__restrict__ xk, int xks, const int32_t *__restrict__ yb, const double *__restrict__ yk, int yks,
+                     const float *__restrict__ factors, int64_t bss, int rows_cap, EvalOut e) {
+    extern __shared__ __attribute__((aligned(16))) float s_rows[];          // [rows_cap][kTW]
+    __shared__ double s_xk[kTW * kMaxK], s_yk[kTH * kMaxK];
+    __shared__ int2 s_xb[kTW], s_yb[kTH];
+    const PlaneTables s{s_xk, s_yk, s_xb, s_yb};
+    const int tid = threadIdx.x, n = blockIdx.z;
+    const int x0 = blockIdx.x * kTW, y0 = blockIdx.y * kTH;
+    const int tw = min(kTW, ow - x0), th = min(kTH, oh - y0);
+    const int xl = tid & 63, yl0 = tid >> 6;
+    const bool in_x = xl < tw;
+    const int64_t npix = (int64_t)oh * ow;
+
+    planes_load_tables(s, xb, xk, xks, yb, yk, yks, iw, ih, x0, y0, tw, th);
+
+    const int r0 = s_yb[0].x;
+    const int rows = min(max(s_yb[th - 1].x + s_yb[th - 1].y - r0, 0), rows_cap);
+    float p[2][kPix];
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+        planes_stage_rows<kCopyX>(src + (int64_t)n * bss + (int64_t)c * ih * iw, s_rows, s, xks, iw, x0, tw, r0, rows);
+        __syncthreads();
+        const float fac = factors ? factors[c] : 1.0f;
+#pragma unroll
+        for (int k = 0; k < kPix; ++k) {
+            const int yl = yl0 + 4 * k;
+            float v = 0.f;
+            if (in_x && yl < th) {
+                v = planes_finish<kCopyY>(s_rows, s, yks, y0, yl, xl, r0, rows_cap);
+                if (factors) v = v * fac;
+            }
+            p[c][k] = v;
+        }
+        __syncthreads();                         // the staged rows of u are read; v (or the reduction) may take the LDS
+    }
+
+    double sum = 0.0;
+    long long cnt[2] = {0, 0};                   // valid, outliers
+#pragma unroll
+    for (int k = 0; k < kPix; ++k) {
+        const int yl = yl0 + 4 * k;
+        if (!in_x || yl >= th) continue;
+        const int64_t pix = (int64_t)(y0 + yl) * ow + x0 + xl;
+        const float pu = p[0][k], pv = p[1][k];
+        if (e.flow) {
+            e.flow[(int64_t)n * 2 * npix + pix] = pu;
+            e.flow[((int64_t)n * 2 + 1) * npix + pix] = pv;
+        }
+        if (e.enc) {
+            const uint32_t eu = encode16(pu), ev = encode16(pv);
+            uint16_t *o = e.enc + ((int64_t)n * npix + pix) * 3;
+            if (e.enc_order == 0) store3_u16(o, 1u, ev, eu);
+            else store3_u16(o, eu, ev, 1u);
+        }
+        if (KIND >= 0) {
+            // a uint16 pixel is three 2-byte loads: a wave's 64 pixels are 384 contiguous bytes and the loads share their cache lines
+            // (as in pwc_kitti_score)
+            float gu, gv;
+            bool ok;
+            if (KIND == 0) {
+                const float *f = static_cast<const float *>(e.gt) + (int64_t)n * 2 * npix + pix;
+                gu = f[0];
+                gv = f[npix];
+                ok = e.valid ? e.valid[(int64_t)n * npix + pix] != 0 : true;
+            } else {
+                const uint16_t *q = static_cast<const uint16_t *>(e.gt) + ((int64_t)n * npix + pix) * 3;
+                gu = ((float)q[KIND == 1 ? 0 : 2] - 32768.0f) / 64.0f;
+                gv = ((float)q[1] - 32768.0f) / 64.0f;
+                ok = q[KIND == 1 ? 2 : 0] != 0;
+            }
+            if (!ok) continue;
+            const float du = pu - gu, dv = pv - gv;
+            const float epe = sqrtf(du * du + dv * dv);
+            const float mag = sqrtf(gu * gu + gv * gv);
+            sum += (double)epe;
+            ++cnt[0];
+            if (epe > fmaxf(3.0f, 0.05f * mag)) ++cnt[1];
+        }
+    }
+    if (KIND >= 0) {
+        // the x coefficient slice was last read before the barriers above
+        pwc::TreeLds<256, 1, 2> &red = *reinterpret_cast<pwc::TreeLds<256, 1, 2> *>(s_xk);
+        pwc::tree_sum(red, &sum, cnt);
+        if (tid == 0) e.part[blockIdx.x + (int64_t)gridDim.x * (blockIdx.y + (int64_t)gridDim.y * blockIdx.z)] = EvalRec{sum, {cnt[0], cnt[1]}};
+    }
+}
+
+// workgroup b adds the tiles of sample b in tile order (as pwc_kitti_score's finish does)
+__global__ __launch_bounds__(256) void pil_flow_eval_finish_kernel(EvalRec *__restrict__ ws, int n, int64_t tiles, float *__restrict__ out) {
+    __shared__ pwc::TreeLds<256, 1, 2> red;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const EvalRec *part = ws + n + (int64_t)b * tiles;
+    double s = 0.0;
+    long long cnt[2] = {0, 0};
+    for (int64_t i = tid; i < tiles; i += 256) {
+        s += part[i].sum;
+        cnt[0] += part[i].count[0];
+        cnt[1] += part[i].count[1];
+    }
+    pwc::tree_sum(red, &s, cnt);
+    if (tid == 0) {
+        ws[b] = EvalRec{s, {cnt[0], cnt[1]}};
+        const long long nv = cnt[0], no = cnt[1];
+        const float nan = __builtin_nanf("");
+        out[2 * b] = nv ? (float)(s / (double)nv) : nan;
+        out[2 * b + 1] = nv ? (float)(100.0 * (double)no / (double)nv) : nan;
     }
 }
 
@@ -321,4 +492,70 @@ extern "C" int pwc_pil_resize_planes_f32(const void *src, void *dst, int n, int 
                        static_cast<float *>(dst), c, in_h, in_w, out_h, out_w, xbounds, xcoef, xksize, ybounds, ycoef, yksize, factors,
                        src_bstride, rows_cap);
     return pwc::check_launch("pil_planes_kernel");
+}
+
+extern "C" int64_t pwc_pil_flow_eval_workspace_bytes(int n, int out_h, int out_w) {
+    if (n <= 0 || out_h <= 0 || out_w <= 0) return -1;
+    return (int64_t)sizeof(EvalRec) * n * (1 + (int64_t)((out_h + kTH - 1) / kTH) * ((out_w + kTW - 1) / kTW));
+}
+
+namespace {
+
+template <int KIND, typename... Args>
+void launch_flow_eval(bool copy_x, bool copy_y, dim3 grid, size_t lds, hipStream_t st, Args... args) {
+    const auto kernel = copy_x ? (copy_y ? pil_flow_eval_kernel<true, true, KIND> : pil_flow_eval_kernel<true, false, KIND>)
+                               : (copy_y ? pil_flow_eval_kernel<false, true, KIND> : pil_flow_eval_kernel<false, false, KIND>);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, st, args...);
+}
+
+}  // namespace
+
+extern "C" int pwc_pil_flow_eval(const void *src, int n, int in_h, int in_w, int out_h, int out_w, const int32_t *xbounds,
+                                 const double *xcoef, int xksize, const int32_t *ybounds, const double *ycoef, int yksize,
+                                 const float *factors, int64_t src_bstride, const void *gt, int gt_kind, const void *valid, void *flow_out,
+                                 void *enc_out, int enc_order, void *workspace, int64_t workspace_bytes, void *out, void *stream) {
+    if (!src || !xbounds || !xcoef || !ybounds || !ycoef) PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: null pointer");
+    if (!gt && !flow_out && !enc_out) PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: nothing requested (gt, flow_out and enc_out are all NULL)");
+    if (gt && (!workspace || !out)) PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: scoring needs workspace and out");
+    if (n <= 0 || in_h <= 0 || in_w <= 0 || out_h <= 0 || out_w <= 0) PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: bad shape");
+    if (!pwc_pil_resize_supported(in_h, in_w, out_h, out_w))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: %dx%d -> %dx%d is outside the supported scale range (downscale <= 8 per axis, more only to outputs shorter than a tile)", in_h, in_w,
+                 out_h, out_w);
+    if (xksize != axis_ksize(in_w, out_w) || yksize != axis_ksize(in_h, out_h))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: ksize (%d, %d) disagrees with the sizes (%d, %d expected)", xksize, yksize,
+                 axis_ksize(in_w, out_w), axis_ksize(in_h, out_h));
+    if (src_bstride < (int64_t)2 * in_h * in_w) PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: batch stride smaller than the tensor");
+    if (gt && (gt_kind < 0 || gt_kind > 2))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: unknown gt_kind %d (0 = float planes, 1 = uint16 {u, v, valid}, 2 = uint16 {valid, v, u})", gt_kind);
+    if (enc_out && (enc_order < 0 || enc_order > 1))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: unknown enc_order %d (0 = {1, v, u}, 1 = {u, v, 1})", enc_order);
+    if (valid && (!gt || gt_kind != 0))
+        PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: valid must be NULL without float ground truth (a uint16 ground truth carries its validity)");
+    if (n > 65535) PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: grid too large (n > 65535)");
+    if (gt) {
+        const int64_t need = pwc_pil_flow_eval_workspace_bytes(n, out_h, out_w);
+        if (workspace_bytes < need)
+            PWC_FAIL(PWC_EINVAL, "pwc_pil_flow_eval: workspace needs %lld bytes, got %lld", (long long)need, (long long)workspace_bytes);
+        if (reinterpret_cast<uintptr_t>(workspace) & 7u) PWC_FAIL(PWC_EALIGN, "pwc_pil_flow_eval: workspace must be 8-byte aligned");
+    }
+    if (pwc::misaligned({src, xbounds, ybounds, factors, flow_out, gt ? out : nullptr}) || pwc::misaligned({xcoef, ycoef}, 8) ||
+        pwc::misaligned({enc_out}, 2) || pwc::misaligned({gt}, gt_kind == 0 ? 4 : 2))
+        PWC_FAIL(PWC_EALIGN, "pwc_pil_flow_eval: needs 4-byte aligned float operands and bounds, 8-byte aligned coefficients and 2-byte aligned uint16 operands");
+    const int rows_cap = span_bound(in_h, out_h, kTH);
+    const bool copy_x = in_w == out_w, copy_y = in_h == out_h;
+    const dim3 grid((out_w + kTW - 1) / kTW, (out_h + kTH - 1) / kTH, n);
+    const size_t lds = rows_cap * kTW * sizeof(float);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    EvalRec *ws = static_cast<EvalRec *>(workspace);
+    const EvalOut e{gt, static_cast<const uint8_t *>(valid), static_cast<float *>(flow_out), static_cast<uint16_t *>(enc_out),
+                    gt ? ws + n : nullptr, enc_order};
+    const float *s = static_cast<const float *>(src);
+#define PWC_EVAL_ARGS s, in_h, in_w, out_h, out_w, xbounds, xcoef, xksize, ybounds, ycoef, yksize, factors, src_bstride, rows_cap, e
+    if (!gt) launch_flow_eval<-1>(copy_x, copy_y, grid, lds, st, PWC_EVAL_ARGS);
+    else if (gt_kind == 0) launch_flow_eval<0>(copy_x, copy_y, grid, lds, st, PWC_EVAL_ARGS);
+    else if (gt_kind == 1) launch_flow_eval<1>(copy_x, copy_y, grid, lds, st, PWC_EVAL_ARGS);
+    else launch_flow_eval<2>(copy_x, copy_y, grid, lds, st, PWC_EVAL_ARGS);
+#undef PWC_EVAL_ARGS
+    if (gt) hipLaunchKernelGGL(pil_flow_eval_finish_kernel, dim3(n), dim3(256), 0, st, ws, n, (int64_t)grid.x * grid.y, static_cast<float *>(out));
+    return pwc::check_launch("pil_flow_eval_kernel");
 }

@@ -565,6 +565,72 @@ def pil_resize_planes(x: torch.Tensor, size: Tuple[int, int], xtab, ytab, factor
     return out
 
 
+def pil_flow_eval_workspace_bytes(n: int, out_h: int, out_w: int) -> int:
+    return _query_bytes(_lib.load().pwc_pil_flow_eval_workspace_bytes(n, out_h, out_w), "pil-flow-eval")
+
+
+_EVAL_WS = {}
+_GT_ORDERS = {"kitti": 1, "reference": 2}
+_ENC_ORDERS = {"reference": 0, "kitti": 1}
+
+
+def pil_flow_eval(x: torch.Tensor, size: Tuple[int, int], xtab, ytab, factors: Optional[torch.Tensor] = None,
+                  gt: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, gt_order: str = "kitti",
+                  enc_out: Optional[torch.Tensor] = None, enc_order: str = "reference", flow_out: Optional[torch.Tensor] = None,
+                  out: Optional[torch.Tensor] = None):
+    """float32 flow [n,2,h,w] (dense planes, free batch stride) resized to (H, W) as pil_resize_planes does (same tables, factors
+    float32 [2] on the device or None) and, in the same launch, scored and / or encoded (C-ABI pwc_pil_flow_eval) -> (scores, totals).
+    gt: torch.uint16 [n,H,W,3], samples {u, v, valid} with gt_order "kitti" or {valid, v, u} with "reference" (`valid` must be None),
+    or float32 [n,2,H,W] with `valid` None / bool / uint8 [n,H,W] (gt_order concerns uint16 samples only).  scores: float32 [n,2] =
+    per-sample (EPE, Fl in percent), NaN without a valid pixel; totals: int64 [n,3] = {bits of the fp64 sum of EPE, #valid, #outliers},
+    a view of the head of the workspace, which is cached per (device, n, H, W) -- consume it before the next call of that shape.  Both
+    are None without gt.  enc_out: contiguous torch.uint16 [n,H,W,3] (2-byte aligned is enough) that receives save_flow's samples,
+    {1, v, u} with enc_order "reference" or {u, v, 1} with "kitti".  flow_out: contiguous float32 [n,2,H,W] that receives the resized
+    flow itself.  At least one of gt / enc_out / flow_out is needed.  Device tensors only, no host synchronisation, bit-reproducible."""
+    if not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 2:
+        raise ValueError("x must be a float32 tensor [n,2,h,w]")
+    x = densify(x)
+    bsx = _plane_dense(x, "x")
+    n, _, h, w = x.shape
+    H, W = (int(v) for v in size)
+    dev = x.device
+    if gt is None and enc_out is None and flow_out is None:
+        raise ValueError("nothing requested: give gt, enc_out or flow_out")
+    if gt_order not in _GT_ORDERS or enc_order not in _ENC_ORDERS:
+        raise ValueError("gt_order / enc_order must be 'kitti' or 'reference', got %r / %r" % (gt_order, enc_order))
+    kind = 0
+    if gt is not None:
+        kind, valid = _kitti_gt_arg(gt, valid, n, H, W, dev)
+        if kind == 1:
+            kind = _GT_ORDERS[gt_order]
+    elif valid is not None:
+        raise ValueError("valid goes with a float32 gt")
+    if enc_out is not None and (enc_out.dtype != torch.uint16 or tuple(enc_out.shape) != (n, H, W, 3) or enc_out.device != dev
+                                or not enc_out.is_contiguous()):
+        raise ValueError("enc_out must be contiguous torch.uint16 %s on %s" % ((n, H, W, 3), dev))
+    if flow_out is not None:
+        _out_arg(flow_out, (n, 2, H, W), torch.float32, dev, contiguous=True)
+    xb, xk, xks = _pil_axis_arg(xtab, W, torch.float64, dev, "x")
+    yb, yk, yks = _pil_axis_arg(ytab, H, torch.float64, dev, "y")
+    fp = None if factors is None else _table_arg(factors, torch.float32, 2, dev, "factors")
+    ws, nb = None, 0
+    with torch.cuda.device(dev):
+        if gt is not None:
+            out = _out_arg(out, (n, 2), torch.float32, dev, contiguous=True)
+            nb = pil_flow_eval_workspace_bytes(n, H, W)
+            key = (dev, n, H, W)
+            ws = _EVAL_WS.get(key)
+            if ws is None:
+                ws = _EVAL_WS[key] = torch.empty(nb // 8, dtype=torch.int64, device=dev)
+        rc = _lib.load().pwc_pil_flow_eval(x.data_ptr(), n, h, w, H, W, xb, xk, xks, yb, yk, yks, fp, bsx, _ptr(gt), kind, _ptr(valid),
+                                           _ptr(flow_out), _ptr(enc_out), _ENC_ORDERS[enc_order], _ptr(ws), nb,
+                                           _ptr(out) if gt is not None else None, _stream(x))
+    check(rc, "pwc_pil_flow_eval")
+    if gt is None:
+        return None, None
+    return out, ws[:3 * n].view(n, 3)
+
+
 def _cv_axis_arg(tab, out_size: int, device, name: str) -> Tuple[int, int]:
     """(first taps int32 [O], weights float32 [O]) of one axis as cv_resize.axis_table makes them, on the device -> their pointers."""
     s0, fx = tab

@@ -14,7 +14,7 @@ composed here from two launches, (H, W) -> (h, W) and (h, W) -> (h, w), each a o
 from __future__ import annotations
 
 import math
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -178,6 +178,19 @@ def resize_frames(frames_u8: torch.Tensor, size, mean=None, std=None, out: Optio
     return (out, u8) if return_u8 else out
 
 
+def _factor_table(factors, c: int, device) -> Optional[torch.Tensor]:
+    """The per-channel factors rounded to float32 as a resident device table (None without factors)."""
+    if factors is None:
+        return None
+    key = (tuple(float(np.float32(f)) for f in factors), str(device))
+    if len(key[0]) != c:
+        raise ValueError("factors must have one entry per channel (%d), got %d" % (c, len(key[0])))
+    fac = _FACTORS.get(key)
+    if fac is None:
+        fac = _FACTORS[key] = torch.tensor(key[0], dtype=torch.float32).to(device)
+    return fac
+
+
 def resize_planes(x: torch.Tensor, size, factors: Optional[Sequence[float]] = None) -> torch.Tensor:
     """float32 planes [n,c,h,w] on the device -> [n,c,H,W] as Pillow resizes mode "F" images; factors: one float per channel,
     multiplied in float32 after the resize."""
@@ -192,15 +205,7 @@ def resize_planes(x: torch.Tensor, size, factors: Optional[Sequence[float]] = No
         h = H
     xt = _axis_tables(w, W, False, x.device)
     yt = _axis_tables(h, H, False, x.device)
-    fac = None
-    if factors is not None:
-        key = (tuple(float(np.float32(f)) for f in factors), str(x.device))
-        if len(key[0]) != c:
-            raise ValueError("factors must have one entry per channel (%d), got %d" % (c, len(key[0])))
-        fac = _FACTORS.get(key)
-        if fac is None:
-            fac = _FACTORS[key] = torch.tensor(key[0], dtype=torch.float32).to(x.device)
-    return ops.pil_resize_planes(x, (H, W), xt, yt, fac)
+    return ops.pil_resize_planes(x, (H, W), xt, yt, _factor_table(factors, c, x.device))
 
 
 def resize_flow(flow: torch.Tensor, size, scale_vectors: bool = True) -> torch.Tensor:
@@ -211,6 +216,55 @@ def resize_flow(flow: torch.Tensor, size, scale_vectors: bool = True) -> torch.T
     H, W = _size(size)
     h, w = flow.shape[2:]
     return resize_planes(flow, (H, W), (W / w, H / h) if scale_vectors else None)
+
+
+class FlowEval(NamedTuple):
+    """What eval_flow hands out; members that were not asked for are None."""
+    scores: Optional[torch.Tensor]       # float32 [B,2] = (EPE, Fl in percent) per sample, NaN without a valid pixel
+    totals: Optional[torch.Tensor]       # int64 [B,3] = {bits of the fp64 sum of EPE, #valid, #outliers}: a view of a cached workspace
+    encoded: Optional[torch.Tensor]      # torch.uint16 [B,H,W,3]: save_flow's samples
+    flow: Optional[torch.Tensor]         # float32 [B,2,H,W]: resize_flow's result
+
+
+def eval_flow(flow: torch.Tensor, size, gt: Optional[torch.Tensor] = None, valid: Optional[torch.Tensor] = None, gt_order: str = "kitti",
+              encode: Optional[str] = None, keep_flow: bool = False, scale_vectors: bool = True, encoded_out: Optional[torch.Tensor] = None,
+              flow_out: Optional[torch.Tensor] = None, scores_out: Optional[torch.Tensor] = None) -> FlowEval:
+    """resize_flow with what inference.py does to its result, in the launch that makes it (ops.pil_flow_eval): [B,2,h,w] is resized
+    to `size` = (H, W) and rescaled exactly as resize_flow does, and then
+      gt given     -> scored: compute_epe / compute_fl of inference.py:105-159 per sample.  gt is torch.uint16 [B,H,W,3] (the PNG's
+                      samples: {u, v, valid} with gt_order "kitti", what kitti.read_png16_rgb returns, or {valid, v, u} with "reference",
+                      the order inference.py's own reader and save_flow use) or float32 [B,2,H,W] with `valid` None / bool / uint8 [B,H,W];
+      encode given -> encoded: save_flow's uint16 samples, "reference" = {1, v, u} (inference.py:266-282), "kitti" = {u, v, 1};
+      keep_flow    -> the float flow itself, bit-equal to resize_flow.
+    No full-resolution float flow is written unless keep_flow asks for it.  `totals` is a view of a workspace cached per shape:
+    consume it before the next call of that shape.  encoded_out / flow_out / scores_out: buffers to fill instead of new tensors
+    (a captured pipeline's static outputs).  Never synchronises; capturable after `prepare(..., frames=False)` or one eager call
+    per geometry.  In Pillow's vertical-first regime (`vertical_first`) the vertical pass runs as its own launch first."""
+    from . import ops
+    if flow.dim() != 4 or flow.shape[1] != 2 or flow.dtype != torch.float32:
+        raise ValueError("flow must be float32 [B,2,h,w], got %s %s" % (flow.dtype, tuple(flow.shape)))
+    if encode not in (None, "kitti", "reference"):
+        raise ValueError("encode must be None, 'kitti' or 'reference', got %r" % (encode,))
+    if gt is None and encode is None and not keep_flow:
+        raise ValueError("nothing requested: give gt, encode or keep_flow")
+    H, W = _size(size)
+    B, _, h, w = flow.shape
+    _check_supported((h, w), (H, W))
+    dev = flow.device
+    fac = _factor_table((W / w, H / h) if scale_vectors else None, 2, dev)      # from the ORIGINAL sizes, as resize_flow
+    if vertical_first((h, w), (H, W)):          # Pillow's order for a tall source: the vertical pass alone, then the fused horizontal one
+        flow = ops.pil_resize_planes(flow, (H, w), _axis_tables(w, w, False, dev), _axis_tables(h, H, False, dev))
+        h = H
+    xt = _axis_tables(w, W, False, dev)
+    yt = _axis_tables(h, H, False, dev)
+    if encode is not None and encoded_out is None:
+        encoded_out = torch.empty((B, H, W, 3), dtype=torch.uint16, device=dev)
+    if keep_flow and flow_out is None:
+        flow_out = torch.empty((B, 2, H, W), dtype=torch.float32, device=dev)
+    scores, totals = ops.pil_flow_eval(flow, (H, W), xt, yt, fac, gt=gt, valid=valid, gt_order=gt_order,
+                                       enc_out=encoded_out if encode is not None else None, enc_order=encode or "reference",
+                                       flow_out=flow_out if keep_flow else None, out=scores_out)
+    return FlowEval(scores, totals, encoded_out if encode is not None else None, flow_out if keep_flow else None)
 
 
 class FrameIngest:
